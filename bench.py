@@ -1,8 +1,13 @@
 """GAN2Shape training-step throughput on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W]        (N > 1 without a launcher: starts
-                                                                 N ranks itself, see self_launch)
+                    [--full] [--dump-outputs DIR]                N ranks itself, see self_launch)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line (iterations/s and
+`ms_per_step`).  `--full` adds everything else the line can carry (below); `--dump-outputs DIR`
+writes what the timed path computes for the last timed step's kind, from the seeded start, as
+DIR/<name>.npy (rerun_from_start, dump_outputs).
 
 Workload (config.workload = "face128_n8"): configs/face.yml restated for the offline box — image
 128x128, StyleGAN2 size 128 / channel_multiplier 1 / z_dim 512, n_proj_samples 8, ellipsoid-prior
@@ -17,7 +22,8 @@ Multi-GPU: the per-image optimisation is independent, so each rank trains its ow
 own model replica and optimisers; no data-path collective (weak scaling).  value = N * K / T with T
 the max over ranks of the barrier-bracketed wall time.
 
-Also reported on the same JSON line: `roofline` of the dominant custom kernels (the fp32-MFMA
+With --full, also reported on the same JSON line: `ms_per_step_kind` (10 extra iterations of
+each kind), `roofline` of the dominant custom kernels (the fp32-MFMA
 convolution kernels — direct implicit GEMM and Winograd F(2x2,3x3): algorithmic direct-convolution
 FLOP / HIP-event time on the launch stream against the 157.3 TFLOP/s fp32 matrix peak, with the
 MFMA-executed rate beside it), `roofline_other` (rasterizer, upfirdn2d, fused_bias_act against the
@@ -421,6 +427,66 @@ def roofline_other(device):
     return out
 
 
+HANDOFF_NAMES = {1: ("normal", "lighting_a", "lighting_b", "albedo", "depth"), 2: ("projected_image", "mask")}
+
+
+def trained_params(trainer):
+    """Every parameter one of the three optimisers updates, once each."""
+    seen, out = set(), []
+    for k in (1, 2, 3):
+        for group in getattr(trainer, f"optim_step{k}").param_groups:
+            for p in group["params"]:
+                if id(p) not in seen:
+                    seen.add(id(p))
+                    out.append(p)
+    return out
+
+
+def rerun_from_start(runner, trainer, start, last_kind):
+    """The timed path (same runner: graph replays in graph mode) run from the seeded start again: the
+    trained parameters get their values from before the first iteration (`start`: (parameter, copy) pairs),
+    every optimiser state tensor (moments, step counters) is zeroed in place as in a fresh optimiser, then
+    one iteration of each kind 1 .. last_kind builds the hand-offs and runs the dumped step.  The
+    trajectory the timed steps follow cannot serve: the default kernels add with float atomics, and ~70
+    Adam iterations turn that rounding into percent-level differences between runs; from the seeded start
+    the results agree to rounding."""
+    with torch.no_grad():
+        for p, p0 in start:
+            p.copy_(p0)
+        for k in (1, 2, 3):
+            for state in getattr(trainer, f"optim_step{k}").state.values():
+                for v in state.values():
+                    if torch.is_tensor(v):
+                        v.zero_()
+    for kind in range(1, last_kind + 1):
+        runner.run(kind)
+    torch.cuda.synchronize()
+
+
+def dump_outputs(directory, runner, kind):
+    """What the runner's latest step of kind `kind` returned (forward_stepK's `loss, collected`), as .npy
+    files in float32 (float64 stays float64): `loss` and the hand-off to the next kind (step 1: normal,
+    lighting_a / _b, albedo, depth; step 2: projected_image, mask; step 3 has none).  Gradients and updated
+    parameters are not written: the backward scatters add with float atomics, which leaves up to ~2e-3 of
+    the largest gradient as run-to-run rounding, and a fresh optimiser's first update (~ +-lr) turns a
+    gradient component rounded across zero into a 2 lr change of its parameter."""
+    import numpy as np
+    g = getattr(runner, "g", None)
+    if g is None or (kind == 1 and getattr(runner, "world", 1) > 1):   # eager runner (or joint step 1 of W > 1)
+        src = runner if g is None else runner.eager
+        loss, collected = src.last_loss[kind], src.collected[kind]
+    else:
+        loss, collected = g.loss[kind], g.collected[kind]
+    out = {"loss": loss}
+    for name, t in zip(HANDOFF_NAMES.get(kind, ()), collected or ()):
+        out[name] = t
+    os.makedirs(directory, exist_ok=True)
+    for name, t in out.items():
+        t = t.detach()
+        np.save(os.path.join(directory, name + ".npy"),
+                t.cpu().numpy() if t.dtype == torch.float64 else t.float().cpu().numpy())
+
+
 def self_launch(n_ranks):
     """`python bench.py --gpus N` without a launcher: start N fresh ranks of this script through
     torch.distributed.run (one process per GPU, rendezvous on 127.0.0.1) as CHILD processes — this
@@ -466,7 +532,14 @@ def main():
     ap.add_argument("--workload", default="face128_n8", choices=sorted(WORKLOADS),
                     help="face128_n8 = the BASELINE metric's configuration (default); face256_fp16 = BASELINE "
                          "config 5 (256x256, fp16-operand MFMA), reported on its own line")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure ms_per_step_kind, roofline (an instrumented eager "
+                         "cycle), roofline_other and cpu_baseline; a plain run reports them as null")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, run the timed path from the seeded start up to the last "
+                         "timed step's kind and write what that step computed as DIR/<name>.npy "
+                         "(see rerun_from_start, dump_outputs)")
     ap.add_argument("--eager", action="store_true", help="launch every kernel from Python (no HIP graphs)")
     ap.add_argument("--deterministic", action="store_true",
                     help="analysis only: g2s_set_deterministic(1) — bit-reproducible iterations (fixed-order "
@@ -474,6 +547,8 @@ def main():
     ap.add_argument("--only", type=int, default=0, choices=[0, 1, 2, 3],
                     help="analysis only: time a single step kind instead of the 7:7:6 mix")
     args = ap.parse_args()
+    if (args.steps is not None and args.steps < 1) or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))   # before anything in this process touches the GPU
@@ -515,6 +590,7 @@ def main():
     image, latent = synthetic_sample(trainer.model, 1234 + rank, device)
     torch.manual_seed(1234 + rank)
     runner = JointStepRunner(trainer, image, latent, world) if joint else StepRunner(trainer, image, latent)
+    start = [(p, p.detach().clone()) for p in trained_params(trainer)] if args.dump_outputs else None
 
     # setup pass (not a benchmark step): one iteration of each kind creates the `collected`
     # hand-offs the trainer would have at this point, and triggers lazy library initialisation
@@ -542,11 +618,11 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # (flops, start event, end event) per g2s_modconv launch, recorded on its launch stream.
+    # (flops, start event, end event) per g2s_modconv launch, recorded on its launch stream (--full).
     # Eager mode: recorded inside the timed region.  Graph mode: HIP events cannot be recorded
     # between the nodes of a replayed graph, so the same launches are timed in an eager pass of
     # one 20-step cycle right after the timed region (same process, same shapes, same kernels).
-    mc.PROFILE = [] if args.eager else None
+    mc.PROFILE = [] if args.eager and args.full else None
     # G2S_BENCH_MARK=1 (profiling runs only): a kernel no training step uses brackets the timed
     # region in a rocprofv3 kernel trace (tools/window_trace.py keeps what lies between the two)
     mark = torch.ones(3, dtype=torch.int32, device=device) if os.environ.get("G2S_BENCH_MARK") else None
@@ -562,25 +638,34 @@ def main():
     if mark is not None:
         mark.bitwise_not()
         torch.cuda.synchronize()
-    # per-kind times (report only): a few iterations of each kind, outside the timed region —
-    # recording events between graph launches costs ~1 ms per iteration
-    for kind in sorted(set(PATTERN)):
-        torch.cuda.synchronize()
-        tk = time.perf_counter()
-        for _ in range(10):
-            runner.run(kind)
-        torch.cuda.synchronize()
-        runner.kind_ms[kind] = (time.perf_counter() - tk) / 10 * 1e3
-    if not args.eager:
-        mc.PROFILE = []
-        # The eager loop is host-bound: an event pair around a small launch would also time the
-        # host's gap before the launch.  Each iteration is therefore queued behind a device-side
-        # spin (~25 ms) so that the host runs ahead and the events bracket back-to-back kernels.
-        for kind in PATTERN:
-            torch.cuda._sleep(50_000_000)
-            eager_runner.run(kind)
-        torch.cuda.synchronize()
-    prof, mc.PROFILE = mc.PROFILE, None
+    final_loss = {f"step{k}": float(v) for k, v in sorted(runner.last_loss.items())}
+    if not all(math.isfinite(v) for v in final_loss.values()):
+        raise RuntimeError(f"non-finite training loss after the timed region: {final_loss}")
+    if args.dump_outputs:
+        last_kind = PATTERN[(args.steps - 1) % len(PATTERN)]
+        rerun_from_start(runner, trainer, start, last_kind)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, runner, last_kind)
+    if args.full:
+        # per-kind times (report only): a few iterations of each kind, outside the timed region —
+        # recording events between graph launches costs ~1 ms per iteration
+        for kind in sorted(set(PATTERN)):
+            torch.cuda.synchronize()
+            tk = time.perf_counter()
+            for _ in range(10):
+                runner.run(kind)
+            torch.cuda.synchronize()
+            runner.kind_ms[kind] = (time.perf_counter() - tk) / 10 * 1e3
+        if not args.eager:
+            mc.PROFILE = []
+            # The eager loop is host-bound: an event pair around a small launch would also time the
+            # host's gap before the launch.  Each iteration is therefore queued behind a device-side
+            # spin (~25 ms) so that the host runs ahead and the events bracket back-to-back kernels.
+            for kind in PATTERN:
+                torch.cuda._sleep(50_000_000)
+                eager_runner.run(kind)
+            torch.cuda.synchronize()
+    prof, mc.PROFILE = mc.PROFILE or [], None
     # what an event pair costs by itself: back-to-back pairs with nothing in between, queued behind a
     # spin like the launches above (a LOWER bound of what the pair adds around a kernel)
     pair_us = None
@@ -598,88 +683,87 @@ def main():
     # whole-job rate: iterations of all ranks / the slowest rank's barrier-bracketed time
     rate, elapsed = sharding.job_throughput(args.steps, elapsed, device)
 
-    final_loss = {f"step{k}": float(v) for k, v in sorted(runner.last_loss.items())}
-    if not all(math.isfinite(v) for v in final_loss.values()):
-        raise RuntimeError(f"non-finite training loss after the timed region: {final_loss}")
     if rank == 0:
-        kind_ms = {k: (v if not isinstance(v, list) else None) for k, v in runner.kind_ms.items()}
-        times = [p[1].elapsed_time(p[2]) for p in prof]
-        flops = sum(p[0] for p in prof)            # algorithmic: direct-convolution FLOP
-        mfma = sum(p[4] for p in prof)             # what the matrix cores execute (Winograd F(2x2): 16 / 36 of it, F(4x4): 36 / 144)
-        ms = sum(times)
-        achieved = flops / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
-        executed = mfma / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
-        per_kernel = {}
-        for name in ("direct", "winograd", "winograd4"):
-            sel = [(p, t) for p, t in zip(prof, times) if p[5] == name]
-            tk = sum(t for _, t in sel)
-            if sel and tk > 0:
-                per_kernel[name] = {"launches": len(sel), "share_of_time": tk / ms,
-                                    "achieved": sum(p[0] for p, _ in sel) / (tk * 1e-3) / 1e12,
-                                    "mfma_executed": sum(p[4] for p, _ in sel) / (tk * 1e-3) / 1e12,
-                                    "avg_launch_us": tk * 1e3 / len(sel)}
-        # executed / algorithmic FLOP of the convolution launches per training iteration (the profiled cycle is one
-        # pass over PATTERN): what rocprofv3's per-iteration kernel time of the same launches is priced against
-        cycle = max(len(PATTERN), 1)
-        exec_gflop_it, algo_gflop_it = mfma / 1e9 / cycle, flops / 1e9 / cycle
-        rocprof = None
-        import glob
-        rp = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_conv_rocprof.json")))
-        if rp and prof and args.workload == "face128_n8" and not args.only and not args.deterministic:
-            with open(rp[-1]) as f:
-                conv_ms = json.load(f)["conv_ms_per_iteration"]
-            rocprof = {"achieved": exec_gflop_it / conv_ms["total"], "frac": exec_gflop_it / conv_ms["total"] / F32_MFMA_PEAK_TFLOPS,
-                       "conv_ms_per_iteration": conv_ms, "source": os.path.relpath(rp[-1], ROOT),
-                       "is": "this run's executed FLOP per iteration / the convolution kernels' time per iteration by rocprofv3 "
-                             "--kernel-trace inside the graph-replayed timed region of the SAME command, read from the committed "
-                             "profiles file (tools/profile_round.sh) — not measured inside this run; the HIP-event figure above "
-                             "carries ~5 us of event-pair cost per launch"}
-        traffic, traffic_src = None, None
-        pmc = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_modconv_pmc.json")))
-        if pmc:  # HBM bytes per launch from separate rocprofv3 --pmc passes of this command
-            with open(pmc[-1]) as f:
-                traffic = json.load(f)["traffic_bytes_per_launch"]
-            traffic_src = os.path.relpath(pmc[-1], ROOT)
-        # `frac` is the fraction of the fp32-MFMA peak the matrix cores actually EXECUTE (a Winograd F(2x2)
-        # launch does 16 multiplications per 4 outputs where the direct convolution does 36, an F(4x4) launch
-        # 36 per 16 instead of 144): the only figure that cannot exceed 1.  The direct-convolution
-        # (algorithmic) rate is kept beside it.  Moving a layer from F(2x2) to F(4x4) LOWERS `frac` (1.78x
-        # fewer FLOP for the same outputs, 1.2x less time) while the algorithmic rate and the step rate rise.
-        roofline = {"bound": "mfma", "achieved": executed, "peak": F32_MFMA_PEAK_TFLOPS,
-                    "unit": "TFLOP/s", "frac": executed / F32_MFMA_PEAK_TFLOPS,
-                    "achieved_is": "FLOP the matrix cores execute / HIP-event time over every launch of the fp32-MFMA "
-                                   "convolution kernels in one 20-step cycle (direct kernel: the algorithmic FLOP of the "
-                                   "convolution; Winograd F(2x2): 16/36 of it; Winograd F(4x4), round 4: 36/144 of it — which is why this "
-                                   "fraction fell from round 3 while the algorithmic rate and iters/s rose)",
-                    "algorithmic": {"achieved": achieved, "frac": achieved / F32_MFMA_PEAK_TFLOPS,
-                                    "is": "direct-convolution FLOP of the same launches / the same time (Winograd "
-                                          "launches alone exceed 1.0 on this scale: not a roofline, a speed-up)"},
-                    "mfma_executed": {"achieved": executed, "frac": executed / F32_MFMA_PEAK_TFLOPS},   # = achieved / frac (kept: round-2 name)
-                    "executed_gflop_per_iteration": exec_gflop_it, "algorithmic_gflop_per_iteration": algo_gflop_it,
-                    "rocprof": rocprof,
-                    # the same with the cost of an EMPTY event pair (measured in this run) taken off every
-                    # launch: still conservative — rocprofv3's own durations (profiles/) are shorter again
-                    "event_pair_overhead_us": pair_us,
-                    "net_of_event_pair": None if not pair_us or ms * 1e3 <= pair_us * len(prof) else {
-                        "achieved": mfma / ((ms * 1e-3) - pair_us * 1e-6 * len(prof)) / 1e12,
-                        "frac": mfma / ((ms * 1e-3) - pair_us * 1e-6 * len(prof)) / 1e12 / F32_MFMA_PEAK_TFLOPS},
-                    "traffic": traffic, "traffic_source": traffic_src,
-                    "traffic_is": "HBM bytes per launch from SEPARATE rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of "
-                                  "tools/pmc_iter.py (same 20-step cycle), read from the committed profiles file — "
-                                  "not measured inside this run",
-                    "algorithmic_bytes_per_launch": (sum(p[3] for p in prof) / len(prof)) if prof else None,
-                    "kernel": "the fp32-MFMA convolution kernels g2s::modconv_kernel (direct implicit GEMM; with "
-                              "g2s::conv_bwd_kernel, the same body next to the weight-gradient GEMM of a layer) + "
-                              "g2s::wino_kernel (Winograd F(2x2,3x3)) + g2s::wino4_kernel (Winograd F(4x4,3x3)): every launch of "
-                              "the 20-step cycle — "
-                              "generator, discriminator, VGG and the small trained nets",
-                    "per_kernel": per_kernel,
-                    "large_launches": _large(prof),
-                    "launches": len(prof), "avg_launch_us": (ms * 1e3 / len(prof)) if prof else None,
-                    "gflop_per_launch": (flops / 1e9 / len(prof)) if prof else None,
-                    "timed_by": "hip events around each launch, " + (
-                        "inside the timed region" if args.eager else
-                        "eager pass of one 20-step cycle after the graph-replayed timed region")}
+        kind_ms = roofline = None
+        if args.full:
+            kind_ms = {k: (v if not isinstance(v, list) else None) for k, v in runner.kind_ms.items()}
+            times = [p[1].elapsed_time(p[2]) for p in prof]
+            flops = sum(p[0] for p in prof)            # algorithmic: direct-convolution FLOP
+            mfma = sum(p[4] for p in prof)             # what the matrix cores execute (Winograd F(2x2): 16 / 36 of it, F(4x4): 36 / 144)
+            ms = sum(times)
+            achieved = flops / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
+            executed = mfma / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
+            per_kernel = {}
+            for name in ("direct", "winograd", "winograd4"):
+                sel = [(p, t) for p, t in zip(prof, times) if p[5] == name]
+                tk = sum(t for _, t in sel)
+                if sel and tk > 0:
+                    per_kernel[name] = {"launches": len(sel), "share_of_time": tk / ms,
+                                        "achieved": sum(p[0] for p, _ in sel) / (tk * 1e-3) / 1e12,
+                                        "mfma_executed": sum(p[4] for p, _ in sel) / (tk * 1e-3) / 1e12,
+                                        "avg_launch_us": tk * 1e3 / len(sel)}
+            # executed / algorithmic FLOP of the convolution launches per training iteration (the profiled cycle is one
+            # pass over PATTERN): what rocprofv3's per-iteration kernel time of the same launches is priced against
+            cycle = max(len(PATTERN), 1)
+            exec_gflop_it, algo_gflop_it = mfma / 1e9 / cycle, flops / 1e9 / cycle
+            rocprof = None
+            import glob
+            rp = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_conv_rocprof.json")))
+            if rp and prof and args.workload == "face128_n8" and not args.only and not args.deterministic:
+                with open(rp[-1]) as f:
+                    conv_ms = json.load(f)["conv_ms_per_iteration"]
+                rocprof = {"achieved": exec_gflop_it / conv_ms["total"], "frac": exec_gflop_it / conv_ms["total"] / F32_MFMA_PEAK_TFLOPS,
+                           "conv_ms_per_iteration": conv_ms, "source": os.path.relpath(rp[-1], ROOT),
+                           "is": "this run's executed FLOP per iteration / the convolution kernels' time per iteration by rocprofv3 "
+                                 "--kernel-trace inside the graph-replayed timed region of the SAME command, read from the committed "
+                                 "profiles file (tools/profile_round.sh) — not measured inside this run; the HIP-event figure above "
+                                 "carries ~5 us of event-pair cost per launch"}
+            traffic, traffic_src = None, None
+            pmc = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_modconv_pmc.json")))
+            if pmc:  # HBM bytes per launch from separate rocprofv3 --pmc passes of this command
+                with open(pmc[-1]) as f:
+                    traffic = json.load(f)["traffic_bytes_per_launch"]
+                traffic_src = os.path.relpath(pmc[-1], ROOT)
+            # `frac` is the fraction of the fp32-MFMA peak the matrix cores actually EXECUTE (a Winograd F(2x2)
+            # launch does 16 multiplications per 4 outputs where the direct convolution does 36, an F(4x4) launch
+            # 36 per 16 instead of 144): the only figure that cannot exceed 1.  The direct-convolution
+            # (algorithmic) rate is kept beside it.  Moving a layer from F(2x2) to F(4x4) LOWERS `frac` (1.78x
+            # fewer FLOP for the same outputs, 1.2x less time) while the algorithmic rate and the step rate rise.
+            roofline = {"bound": "mfma", "achieved": executed, "peak": F32_MFMA_PEAK_TFLOPS,
+                        "unit": "TFLOP/s", "frac": executed / F32_MFMA_PEAK_TFLOPS,
+                        "achieved_is": "FLOP the matrix cores execute / HIP-event time over every launch of the fp32-MFMA "
+                                       "convolution kernels in one 20-step cycle (direct kernel: the algorithmic FLOP of the "
+                                       "convolution; Winograd F(2x2): 16/36 of it; Winograd F(4x4), round 4: 36/144 of it — which is why this "
+                                       "fraction fell from round 3 while the algorithmic rate and iters/s rose)",
+                        "algorithmic": {"achieved": achieved, "frac": achieved / F32_MFMA_PEAK_TFLOPS,
+                                        "is": "direct-convolution FLOP of the same launches / the same time (Winograd "
+                                              "launches alone exceed 1.0 on this scale: not a roofline, a speed-up)"},
+                        "mfma_executed": {"achieved": executed, "frac": executed / F32_MFMA_PEAK_TFLOPS},   # = achieved / frac (kept: round-2 name)
+                        "executed_gflop_per_iteration": exec_gflop_it, "algorithmic_gflop_per_iteration": algo_gflop_it,
+                        "rocprof": rocprof,
+                        # the same with the cost of an EMPTY event pair (measured in this run) taken off every
+                        # launch: still conservative — rocprofv3's own durations (profiles/) are shorter again
+                        "event_pair_overhead_us": pair_us,
+                        "net_of_event_pair": None if not pair_us or ms * 1e3 <= pair_us * len(prof) else {
+                            "achieved": mfma / ((ms * 1e-3) - pair_us * 1e-6 * len(prof)) / 1e12,
+                            "frac": mfma / ((ms * 1e-3) - pair_us * 1e-6 * len(prof)) / 1e12 / F32_MFMA_PEAK_TFLOPS},
+                        "traffic": traffic, "traffic_source": traffic_src,
+                        "traffic_is": "HBM bytes per launch from SEPARATE rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of "
+                                      "tools/pmc_iter.py (same 20-step cycle), read from the committed profiles file — "
+                                      "not measured inside this run",
+                        "algorithmic_bytes_per_launch": (sum(p[3] for p in prof) / len(prof)) if prof else None,
+                        "kernel": "the fp32-MFMA convolution kernels g2s::modconv_kernel (direct implicit GEMM; with "
+                                  "g2s::conv_bwd_kernel, the same body next to the weight-gradient GEMM of a layer) + "
+                                  "g2s::wino_kernel (Winograd F(2x2,3x3)) + g2s::wino4_kernel (Winograd F(4x4,3x3)): every launch of "
+                                  "the 20-step cycle — "
+                                  "generator, discriminator, VGG and the small trained nets",
+                        "per_kernel": per_kernel,
+                        "large_launches": _large(prof),
+                        "launches": len(prof), "avg_launch_us": (ms * 1e3 / len(prof)) if prof else None,
+                        "gflop_per_launch": (flops / 1e9 / len(prof)) if prof else None,
+                        "timed_by": "hip events around each launch, " + (
+                            "inside the timed region" if args.eager else
+                            "eager pass of one 20-step cycle after the graph-replayed timed region")}
         out = {
             "metric": "GAN2Shape step iters/sec, faces 128\u00d7128 b=8, 1/2/4/8 MI355X",  # BASELINE.json's string
             "value": rate, "unit": "iters/s", "n_gpus": world,
@@ -699,16 +783,16 @@ def main():
                                     "all ranks" if joint else "one image per rank, no collective"),
                        **({"deterministic": "g2s_set_deterministic(1): bit-reproducible iterations (analysis run, "
                                             "not the BASELINE metric)"} if args.deterministic else {})},
-            "ms_per_step_kind": {f"step{k}": v for k, v in kind_ms.items()},
+            "ms_per_step_kind": {f"step{k}": v for k, v in kind_ms.items()} if args.full else None,
             "launch_mode": "eager" if args.eager else (
                 "hipGraph replay: two segments per step kind (forward + backward + bucket pack | optimiser step) with the "
                 "gradient all-reduce between them" if joint else "hipGraph replay (one graph per step kind)"),
             "final_loss": final_loss,
             "roofline": roofline,
-            "roofline_other": roofline_other(device) if world == 1 and args.workload == "face128_n8"
+            "roofline_other": roofline_other(device) if args.full and world == 1 and args.workload == "face128_n8"
             and not args.deterministic else None,
         }
-        if cfg['mfma_operands'] == 'f16':
+        if roofline is not None and cfg['mfma_operands'] == 'f16':
             # priced against the dense fp16 MFMA peak (MI355X_MICROARCH.md: ~2.5 PFLOP/s); every launch of this workload's
             # frozen networks runs fp16 operands / fp32 accumulation, the trained nets' launches stay fp32
             f16_peak = 2500.0
@@ -717,7 +801,7 @@ def main():
             r["peak"], r["frac"] = f16_peak, r["achieved"] / f16_peak
             r["peak_note"] = ("dense fp16 MFMA peak; the kernels are bound by the fp32 -> fp16 operand conversion (activations stay "
                               "fp32 in HBM, DESIGN.md section 4.4), not by the matrix pipe")
-        if world == 1 and not args.no_cpu_baseline and args.workload == "face128_n8":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "face128_n8":
             out["cpu_baseline"] = cpu_baseline(args.n_proj)
         else:
             out["cpu_baseline"] = None

@@ -875,9 +875,55 @@ def gan_golden():
     np.savez_compressed(os.path.join(OUT, "gan128.npz"), **out)
 
 
+def modules_golden():
+    """The reference's module structure and the data its loaders read, so that the tests need no
+    reference tree: (a) the five small nets of GAN2Shape/networks.py — state-dict layout and their
+    outputs with seeded weights (model_cases.fill_scaled, sorted key order) on a seeded input;
+    (b) the state-dict layout of the vendored StyleGAN2 Generator / Discriminator
+    (stylegan2-pytorch/model.py) at the two sizes the tests use; (c) the key list of the LPIPS
+    `lpips/weights/v0.1/vgg.pth` file (its values are lpips.npz `lin{k}`); (d) the items
+    GAN2Shape/dataset.py:ImageLatentDataset returns for model_cases.write_toy_image_dataset."""
+    sys.path.insert(0, os.path.dirname(OUT))
+    sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
+    import tempfile
+    import gan2shape_amd  # noqa: F401
+    import model_cases as mc
+    sys.path.insert(0, REF)
+    sys.path.insert(0, SG2)
+    from GAN2Shape import dataset as ref_dataset
+    from GAN2Shape import networks as ref_networks
+    import model as sg2
+    out = {}
+    x = mc.small_net_input()
+    for name in mc.SMALL_NETS:
+        r = getattr(ref_networks, name)(128)
+        keys, shapes = mc.state_dict_layout(r)
+        out[f"net.{name}.keys"], out[f"net.{name}.shapes"] = np.array(keys), shapes
+        mc.fill_scaled(r, mc.SMALL_NET_SEED)
+        with torch.no_grad():
+            out[f"net.{name}.y"] = np_(r(x))
+    for size, cm in mc.STYLEGAN2_CASES:
+        for cls, args in (("Generator", (size, 512, 8)), ("Discriminator", (size,))):
+            keys, shapes = mc.state_dict_layout(getattr(sg2, cls)(*args, channel_multiplier=cm))
+            out[f"sg2.{cls}.{size}_{cm}.keys"], out[f"sg2.{cls}.{size}_{cm}.shapes"] = np.array(keys), shapes
+    sd = torch.load(os.path.join(SG2, "lpips/weights/v0.1/vgg.pth"), map_location="cpu", weights_only=True)
+    out["vgg_pth.keys"] = np.array(list(sd.keys()))
+    lp = np.load(os.path.join(OUT, "lpips.npz"))
+    assert all(np.array_equal(np_(v), lp[f"lin{k}"]) for k, v in enumerate(sd.values()))
+    with tempfile.TemporaryDirectory() as root:
+        mc.write_toy_image_dataset(root)
+        from gan2shape_amd import dataset   # the transform both sides are fed (the reference takes one from main.py)
+        ds = ref_dataset.ImageLatentDataset(root, transform=dataset.default_transform(32), subset=[1, 2, 0])
+        out["dataset.len"] = np.array(len(ds))
+        for i in range(len(ds)):
+            image, latent, index = ds[i]
+            out[f"dataset.{i}.image"], out[f"dataset.{i}.latent"], out[f"dataset.{i}.index"] = np_(image), np_(latent), np.array(index)
+    np.savez_compressed(os.path.join(OUT, "modules.npz"), **out)
+
+
 if __name__ == "__main__":
-    # python tests/golden/make_golden.py [ops geometry misc gan model steps trainer lpips]   (default: all)
-    for name in sys.argv[1:] or ["ops", "geometry", "misc", "gan", "model", "steps", "trainer", "lpips"]:
+    # python tests/golden/make_golden.py [ops geometry misc gan model steps trainer lpips modules]   (default: all)
+    for name in sys.argv[1:] or ["ops", "geometry", "misc", "gan", "model", "steps", "trainer", "lpips", "modules"]:
         globals()[f"{name}_golden"]()
     for f in sorted(os.listdir(OUT)):
         if f.endswith(".npz"):

@@ -316,6 +316,46 @@ TOY_STAGES = [{'step1': 2, 'step2': 1, 'step3': 2}, {'step1': 1, 'step2': 3, 'st
 TOY_CFG = {"image_size": 8, "category": "face", "n_proj_samples": 3, "n_epochs_prior": 2, "prior_name": "ellipsoid"}
 
 
+def write_toy_image_dataset(root):
+    """A seeded three-image dataset in the layout of GAN2Shape/dataset.py:8-79: `list.txt`, PNGs of three
+    aspect ratios and latent files in the three formats the loader accepts (tensor, {'latent': w},
+    {name: {'latent': w}}; one of them 10 x 512)."""
+    import os
+
+    import numpy as np
+    from PIL import Image
+    rng = np.random.default_rng(0)
+    g = torch.Generator().manual_seed(0)
+    os.makedirs(os.path.join(root, "latents"))
+    names = []
+    for i, (w, h) in enumerate([(40, 40), (48, 36), (30, 50)]):
+        name = f"img_{i}.png"
+        Image.fromarray(rng.integers(0, 256, (h, w, 3), dtype=np.uint8)).save(os.path.join(root, name))
+        names.append(name)
+        lat = torch.randn(1, 512, generator=g) if i != 1 else torch.randn(10, 512, generator=g)
+        obj = lat if i == 0 else ({"latent": lat} if i == 1 else {name: {"latent": lat}})
+        torch.save(obj, os.path.join(root, "latents", f"img_{i}.pt"))
+    with open(os.path.join(root, "list.txt"), "w") as f:
+        f.write("\n".join(names) + "\n")
+
+
+# ---- the reference's modules, pinned by structure (tests/golden/modules.npz)
+SMALL_NETS = ["DepthNet", "AlbedoNet", "ViewpointNet", "LightingNet", "OffsetEncoder"]
+SMALL_NET_SEED = 41
+STYLEGAN2_CASES = [(128, 1), (64, 2)]
+
+
+def small_net_input():
+    return torch.randn(2, 3, 128, 128, generator=torch.Generator().manual_seed(0))
+
+
+def state_dict_layout(module):
+    """(keys in state-dict order, shapes padded with -1 to 5 dimensions)."""
+    sd = module.state_dict()
+    shapes = [list(v.shape) + [-1] * (5 - v.dim()) for v in sd.values()]
+    return list(sd.keys()), torch.tensor(shapes, dtype=torch.int64).numpy()
+
+
 # ---- directional gradient evidence of a whole step (steps.npz `*.gproj.*`, `*.gtnorm.*`)
 N_PROBES = 6
 

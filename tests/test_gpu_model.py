@@ -645,6 +645,38 @@ def test_bench_self_launches_ranks():
     assert line["scaling"] == "weak" and line["cpu_baseline"] is None
 
 
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain run times exactly --steps steps, reports ms_per_step and none of the --full figures;
+    --dump-outputs writes the results of the last timed step's kind (here step 1 of the 7:7:6 cycle)
+    as float32 .npy, and two runs with the same arguments write the same results up to rounding."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    dumps = []
+    for run in range(2):
+        d = str(tmp_path / f"run{run}")
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", d], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                           text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "iters/s" and line["higher_is_better"]
+        assert abs(line["value"] * line["ms_per_step"] - 1e3) < 1e-6 * 1e3
+        assert all(line[k] is None for k in ("roofline", "roofline_other", "cpu_baseline", "ms_per_step_kind"))
+        dumps.append({f: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+    a, b = dumps
+    assert set(a) == {f"{n}.npy" for n in ("loss", "normal", "lighting_a", "lighting_b", "albedo", "depth")}
+    assert all(x.dtype == np.float32 and np.isfinite(x).all() for x in a.values())
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    for f in a:
+        # the default kernels add with float atomics: summation-order rounding only (the normals, built from
+        # differences of neighbouring depths, carry the most: 7.8e-5 measured)
+        np.testing.assert_allclose(b[f], a[f], rtol=1e-4, atol=5e-4 * float(np.abs(a[f]).max()), err_msg=f)
+
+
 def test_config5_fp16_operands_and_256():
     """BASELINE config 5 (256x256 face, confidence-map prior, fp16-operand MFMA): (a) the generator
     with fp16 operands stays within 1e-2 of its fp32 output, latent gradient within

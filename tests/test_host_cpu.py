@@ -1,10 +1,9 @@
 """-m "not gpu": host logic that needs no kernel — the geometry mirror against the golden vectors,
-losses, resize, priors, state-dict compatibility with the reference modules (live, in the build
-container only), the C-ABI surface, sharding helpers."""
+losses, resize, priors, state-dict compatibility with the reference modules (tests/golden/modules.npz),
+the C-ABI surface, sharding helpers."""
 import math
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
@@ -16,9 +15,6 @@ from gan2shape_amd.renderer import Renderer
 from gan2shape_amd.renderer import utils as ru
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-SG2 = os.path.join(REF, "GAN2Shape/stylegan2/stylegan2-pytorch")
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree only exists in the build container")
 
 
 def T(a):
@@ -386,48 +382,53 @@ def test_joint_trainer_fit_follows_reference_run(golden):
     np.testing.assert_allclose(params, g["joint.params"], rtol=1e-5, atol=1e-6)
 
 
-# ----------------------------------------------------------------------------- reference (live)
-def _ref_sg2():
-    if SG2 not in sys.path:
-        sys.path.insert(0, SG2)
-    import model as ref_sg2
-    return ref_sg2
+# ----------------------------------------------------------------------------- reference modules (fixture)
+def _layout_equal(module, g, prefix):
+    """The module's state dict has the reference's keys, in the reference's order, with its shapes
+    (tests/golden/modules.npz: make_golden.modules_golden), and loads a dict of that layout strictly."""
+    import model_cases as mc
+    keys, shapes = mc.state_dict_layout(module)
+    assert keys == g[f"{prefix}.keys"].tolist()
+    np.testing.assert_array_equal(shapes, g[f"{prefix}.shapes"])
+    module.load_state_dict({k: torch.zeros([d for d in s if d >= 0]) for k, s in zip(keys, g[f"{prefix}.shapes"])},
+                           strict=True)
 
 
-@needs_ref
-def test_small_nets_equal_reference():
-    sys.path.insert(0, REF)
-    from GAN2Shape import networks as ref
-    torch.manual_seed(0)
-    x = torch.randn(2, 3, 128, 128)
-    for name in ["DepthNet", "AlbedoNet", "ViewpointNet", "LightingNet", "OffsetEncoder"]:
-        r = getattr(ref, name)(128)
+def test_small_nets_equal_reference(golden):
+    """The five small nets have the reference's state-dict layout (GAN2Shape/networks.py) and, with the
+    same seeded weights, compute its outputs.  The fixture was computed by the reference on another
+    host's CPU kernels: equal up to float32 summation order."""
+    import model_cases as mc
+    g = golden("modules")
+    x = mc.small_net_input()
+    for name in mc.SMALL_NETS:
         m = getattr(networks, name)(128)
-        m.load_state_dict(r.state_dict(), strict=True)
+        _layout_equal(m, g, f"net.{name}")
+        mc.fill_scaled(m, mc.SMALL_NET_SEED)
         with torch.no_grad():
-            torch.testing.assert_close(m(x), r(x), rtol=0, atol=0)
+            y = m(x)
+        ref = torch.from_numpy(g[f"net.{name}.y"])
+        torch.testing.assert_close(y, ref, rtol=1e-5, atol=1e-5 * float(ref.abs().max()), msg=name)
     m64 = networks.OffsetEncoder(64)
     assert m64(torch.randn(1, 3, 64, 64)).shape == (1, 512)
 
 
-@needs_ref
 @pytest.mark.parametrize("size,cm", [(128, 1), (64, 2)])
-def test_stylegan2_state_dict_compatible(size, cm):
-    ref = _ref_sg2()
+def test_stylegan2_state_dict_compatible(golden, size, cm):
     from gan2shape_amd import stylegan2 as sg2
+    g = golden("modules")
     for cls, args in (("Generator", (size, 512, 8)), ("Discriminator", (size,))):
-        r = getattr(ref, cls)(*args, channel_multiplier=cm)
-        m = getattr(sg2, cls)(*args, channel_multiplier=cm)
-        rs, ms = r.state_dict(), m.state_dict()
-        assert list(rs.keys()) == list(ms.keys())
-        assert all(rs[k].shape == ms[k].shape for k in rs)
-        m.load_state_dict(rs, strict=True)
+        _layout_equal(getattr(sg2, cls)(*args, channel_multiplier=cm), g, f"sg2.{cls}.{size}_{cm}")
 
 
-@needs_ref
-def test_lpips_state_dict_keys_match_reference_weight_file():
+def test_lpips_state_dict_keys_match_reference_weight_file(golden, tmp_path):
+    """The reference's `lpips/weights/v0.1/vgg.pth` (its key list: modules.npz; its values: lpips.npz),
+    written back as the file it is — a state dict saved with torch.save — and loaded from disk."""
     from gan2shape_amd.lpips import PerceptualLoss
-    path = os.path.join(SG2, "lpips/weights/v0.1/vgg.pth")
+    keys = golden("modules")["vgg_pth.keys"].tolist()
+    lins = golden("lpips")
+    path = str(tmp_path / "vgg.pth")
+    torch.save({k: torch.from_numpy(lins[f"lin{i}"]) for i, k in enumerate(keys)}, path)
     sd = torch.load(path, map_location="cpu", weights_only=True)
     p = PerceptualLoss()
     own = p.net.state_dict()
@@ -486,28 +487,13 @@ def test_shard_indices_partition():
 
 
 # ----------------------------------------------------------------------------- dataset format
-def _make_dataset(root):
-    from PIL import Image
-    rng = np.random.default_rng(0)
-    os.makedirs(os.path.join(root, "latents"))
-    names = []
-    for i, (w, h) in enumerate([(40, 40), (48, 36), (30, 50)]):
-        name = f"img_{i}.png"
-        Image.fromarray(rng.integers(0, 256, (h, w, 3), dtype=np.uint8)).save(os.path.join(root, name))
-        names.append(name)
-        lat = torch.randn(1, 512) if i != 1 else torch.randn(10, 512)
-        obj = lat if i == 0 else ({"latent": lat} if i == 1 else {name: {"latent": lat}})
-        torch.save(obj, os.path.join(root, "latents", f"img_{i}.pt"))
-    with open(os.path.join(root, "list.txt"), "w") as f:
-        f.write("\n".join(names) + "\n")
-
-
 def test_dataset_formats(tmp_path):
     """list.txt + latents/*.pt layout of GAN2Shape/dataset.py:8-79 (tensor, {'latent': w} and
     {name: {'latent': w}} latent files; subsets; [-1, 1] images)."""
     from gan2shape_amd import dataset
+    import model_cases as mc
     root = str(tmp_path)
-    _make_dataset(root)
+    mc.write_toy_image_dataset(root)
     ds = dataset.ImageLatentDataset(root, transform=dataset.default_transform(32))
     assert len(ds) == 3
     shapes = [(3, 32, 32), (3, 32, 42), (3, 53, 32)]
@@ -522,20 +508,21 @@ def test_dataset_formats(tmp_path):
         dataset.ImageDataset(root, subset=[5])
 
 
-@needs_ref
-def test_dataset_equals_reference(tmp_path):
-    sys.path.insert(0, REF)
-    from GAN2Shape import dataset as ref
+def test_dataset_equals_reference(golden, tmp_path):
+    """ImageLatentDataset against the items the reference's GAN2Shape/dataset.py returned for the same
+    files (tests/golden/modules.npz), through the same transform."""
+    import model_cases as mc
     from gan2shape_amd import dataset
+    g = golden("modules")
     root = str(tmp_path)
-    _make_dataset(root)
-    tf = dataset.default_transform(32)
-    a = dataset.ImageLatentDataset(root, transform=tf, subset=[1, 2, 0])
-    b = ref.ImageLatentDataset(root, transform=tf, subset=[1, 2, 0])
-    assert len(a) == len(b)
+    mc.write_toy_image_dataset(root)
+    a = dataset.ImageLatentDataset(root, transform=dataset.default_transform(32), subset=[1, 2, 0])
+    assert len(a) == int(g["dataset.len"])
     for i in range(len(a)):
-        (ia, la, xa), (ib, lb, xb) = a[i], b[i]
-        assert xa == xb and torch.equal(ia, ib) and torch.equal(la, lb)
+        image, latent, index = a[i]
+        assert index == int(g[f"dataset.{i}.index"])
+        assert torch.equal(image, torch.from_numpy(g[f"dataset.{i}.image"]))
+        assert torch.equal(latent, torch.from_numpy(g[f"dataset.{i}.latent"]))
 
 
 def test_pass_arena_slices_and_fallbacks():
