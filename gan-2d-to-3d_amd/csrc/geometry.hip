@@ -459,10 +459,10 @@ extern "C" int g2s_warp_verts_fwd(const float *depth, const float *rays, const f
 
 extern "C" int g2s_warp_verts_bwd(const float *depth, const float *rays, const float *R,
                                   const float *gverts, float rot_center_depth, float *gdepth,
-                                  float *gRt, int B, int P, g2s_stream_t stream) {
+                                  float *gRt, int B, int P, int acc_is_zero, g2s_stream_t stream) {
     G2S_REQUIRE(depth && rays && R && gverts && gdepth && B > 0 && P > 0 && B <= 65535, "bad argument");
     hipStream_t st = as_stream(stream);
-    if (gRt && !precleared() && hipMemsetAsync(gRt, 0, (size_t)B * 12 * sizeof(float), st) != hipSuccess)
+    if (gRt && !acc_is_zero && hipMemsetAsync(gRt, 0, (size_t)B * 12 * sizeof(float), st) != hipSuccess)
         return fail(G2S_ERR_LAUNCH, "hipMemsetAsync failed");
     warp_verts_bwd<<<dim3(deterministic() ? 1 : cdiv(P, 256), B), 256, 0, st>>>(depth, rays, R, gverts, rot_center_depth, gdepth, gRt, P, gRt != nullptr);
     return check_launch("g2s_warp_verts_bwd");
@@ -480,10 +480,10 @@ extern "C" int g2s_inv_warp_grid_fwd(const float *depth, const float *rays, cons
 extern "C" int g2s_inv_warp_grid_bwd(const float *depth, const float *rays, const float *R,
                                      const float *t, const float *K, float rot_center_depth,
                                      const float *ggrid, float *gdepth, float *gRt, int B, int H,
-                                     int W, g2s_stream_t stream) {
+                                     int W, int acc_is_zero, g2s_stream_t stream) {
     G2S_REQUIRE(depth && rays && R && t && K && ggrid && gdepth && B > 0 && H > 1 && W > 1 && B <= 65535, "bad argument");
     hipStream_t st = as_stream(stream);
-    if (gRt && !precleared() && hipMemsetAsync(gRt, 0, (size_t)B * 12 * sizeof(float), st) != hipSuccess)
+    if (gRt && !acc_is_zero && hipMemsetAsync(gRt, 0, (size_t)B * 12 * sizeof(float), st) != hipSuccess)
         return fail(G2S_ERR_LAUNCH, "hipMemsetAsync failed");
     inv_warp_grid_bwd<<<dim3(deterministic() ? 1 : cdiv(H * W, 256), B), 256, 0, st>>>(
         depth, rays, R, t, rot_center_depth, make_intr(K, H, W), ggrid, gdepth, gRt, H * W, gRt != nullptr);
@@ -496,12 +496,13 @@ static void smooth_weights(int N, int H, int W, float &wxx, float &wxy, float &w
     wxy = (H > 1 && W > 1) ? 2.0f / ((float)N * (H - 1) * (W - 1)) : 0.0f;  // dxdy and dydx
 }
 
-extern "C" int g2s_smooth_loss_fwd(const float *p, float *loss, int N, int H, int W, g2s_stream_t stream) {
+extern "C" int g2s_smooth_loss_fwd(const float *p, float *loss, int N, int H, int W, int acc_is_zero,
+                                   g2s_stream_t stream) {
     G2S_REQUIRE(p && loss && N > 0 && H > 0 && W > 0 && N <= 65535, "bad argument");
     float wxx, wxy, wyy;
     smooth_weights(N, H, W, wxx, wxy, wyy);
     hipStream_t st = as_stream(stream);
-    if (!precleared() && hipMemsetAsync(loss, 0, sizeof(float), st) != hipSuccess) return fail(G2S_ERR_LAUNCH, "hipMemsetAsync failed");
+    if (!acc_is_zero && hipMemsetAsync(loss, 0, sizeof(float), st) != hipSuccess) return fail(G2S_ERR_LAUNCH, "hipMemsetAsync failed");
     smooth_loss_fwd<<<deterministic() ? dim3(1, 1, 1) : dim3(cdiv(W, 32), cdiv(H, 8), N), 256, 0, st>>>(p, loss, N, H, W, wxx, wxy, wyy);
     return check_launch("g2s_smooth_loss_fwd");
 }
@@ -540,13 +541,13 @@ extern "C" int g2s_shading_fwd(const float *normal, const float *light, const fl
 
 extern "C" int g2s_shading_bwd(const float *normal, const float *light, const float *albedo,
                                const float *gdiffuse, const float *gtexture, float *gnormal,
-                               float *galbedo, float *glight, int B, int Bn, int Ba, int P,
+                               float *galbedo, float *glight, int B, int Bn, int Ba, int P, int acc_is_zero,
                                g2s_stream_t stream) {
     G2S_REQUIRE(normal && light && albedo && gtexture && gnormal && galbedo && glight && B > 0 && P > 0 && B <= 65535,
                 "bad argument");
     G2S_REQUIRE((Bn == 1 || Bn == B) && (Ba == 1 || Ba == B), "normal / albedo batch must be 1 or B");
     hipStream_t st = as_stream(stream);
-    if (!precleared() && hipMemsetAsync(glight, 0, (size_t)B * 4 * sizeof(float), st) != hipSuccess)
+    if (!acc_is_zero && hipMemsetAsync(glight, 0, (size_t)B * 4 * sizeof(float), st) != hipSuccess)
         return fail(G2S_ERR_LAUNCH, "hipMemsetAsync failed");
     shading_bwd<<<dim3(deterministic() ? 1 : cdiv(P, 256), B), 256, 0, st>>>(normal, light, albedo, gdiffuse, gtexture, gnormal, galbedo, glight, P, Bn, Ba);
     return check_launch("g2s_shading_bwd");
@@ -562,10 +563,10 @@ extern "C" int g2s_depth_head_fwd(const float *raw, const float *mean, float *ou
 
 extern "C" int g2s_depth_head_bwd(const float *raw, const float *mean, const float *g, float *g_raw, float *gsum,
                                   int64_t n, int W, float lo, float hi, int clamp_border, float border_depth,
-                                  g2s_stream_t stream) {
+                                  int acc_is_zero, g2s_stream_t stream) {
     G2S_REQUIRE(raw && mean && g && g_raw && gsum && n > 0 && W >= 4 && n % W == 0, "bad argument");
     hipStream_t st = as_stream(stream);
-    if (!precleared() && hipMemsetAsync(gsum, 0, sizeof(float), st) != hipSuccess) return fail(G2S_ERR_LAUNCH, "hipMemsetAsync failed");
+    if (!acc_is_zero && hipMemsetAsync(gsum, 0, sizeof(float), st) != hipSuccess) return fail(G2S_ERR_LAUNCH, "hipMemsetAsync failed");
     const int blocks = deterministic() ? 1 : (int)std::min<long>(cdiv((long)n, 256), 1024);
     depth_head_bwd<<<blocks, 256, 0, st>>>(raw, mean, g, g_raw, gsum, (long)n, DepthHead{lo, hi, border_depth, W, clamp_border});
     sub_mean_kernel<<<cdiv((long)n, 256), 256, 0, st>>>(g_raw, gsum, (long)n);

@@ -1066,15 +1066,20 @@ struct WgradRider {
     bool dw_is_zero;
 };
 
-// Noise term of the epilogue for the NEXT launch of this thread (set and cleared by g2s_modconv_nba around its call:
-// an implementation detail of this file, no state survives an entry point).
-static thread_local const float *t_noise = nullptr, *t_noise_w = nullptr;
+// The epilogue of one launch: y = gain * act(sum + noise_w[0] * noise[oy, ox] + bias[m]), act 1 = leaky-ReLU(alpha),
+// 0 = none (gain unused).  NULL pointers drop their term; only g2s_modconv_nba passes a noise (with a bias, act 1).
+struct Epilogue {
+    const float *bias, *noise, *noise_w;
+    int act;
+    float alpha, gain;
+};
+static const Epilogue kNoEpilogue{nullptr, nullptr, nullptr, 0, 0.0f, 1.0f};
 
 static int conv_launch(const float *x, const float *w, const float *in_scale, const float *out_scale,
-                       const float *bias, int act, float act_alpha, float act_gain, float *y, int B,
-                       int Cr, int M, int H, int W, const ConvGeom &g, int tuned_tile, int tuned_splitk,
-                       g2s_stream_t stream, bool y_is_zero = false, bool f16_operands = false, int groups = 1,
-                       const WgradRider *rider = nullptr, int *plan_needs_zero = nullptr) {
+                       const Epilogue &ep, float *y, int B, int Cr, int M, int H, int W, const ConvGeom &g,
+                       int tuned_tile, int tuned_splitk, g2s_stream_t stream, bool y_is_zero = false,
+                       bool f16_operands = false, int groups = 1, const WgradRider *rider = nullptr,
+                       int *plan_needs_zero = nullptr) {
     G2S_REQUIRE(plan_needs_zero || (x && w && y), "x, w, y must not be NULL");
     G2S_REQUIRE(B > 0 && Cr > 0 && M > 0 && H > 0 && W > 0, "sizes must be positive");
     const int k = g.k, s_ = g.stride, p_ = g.pad, KK = k * k;
@@ -1086,13 +1091,13 @@ static int conv_launch(const float *x, const float *w, const float *in_scale, co
     d.w = w;
     d.in_scale = in_scale;
     d.out_scale = out_scale;
-    d.bias = bias;
-    d.noise = t_noise;
-    d.noise_w = t_noise_w;
+    d.bias = ep.bias;
+    d.noise = ep.noise;
+    d.noise_w = ep.noise_w;
     G2S_REQUIRE(!d.noise || (!f16_operands && groups == 1), "the noise epilogue exists for the fp32 kernel only");
-    d.act = act;
-    d.act_alpha = act_alpha;
-    d.act_gain = act_gain;
+    d.act = ep.act;
+    d.act_alpha = ep.alpha;
+    d.act_gain = ep.gain;
     d.y = y;
     d.B = B;
     d.H = H;
@@ -1194,8 +1199,7 @@ static int conv_launch(const float *x, const float *w, const float *in_scale, co
     // A bias / activation epilogue needs the complete sum: with split-K it runs as a second,
     // elementwise launch (g2s_fused_bias_act in place) after the partial sums have been added.
     const bool split = splitk > 1;
-    const bool deferred_epilogue = split && (bias != nullptr || act != 0 || d.noise != nullptr);
-    const float *noise = d.noise, *noise_w = d.noise_w;
+    const bool deferred_epilogue = split && (ep.bias != nullptr || ep.act != 0 || ep.noise != nullptr);
     if (deferred_epilogue) {
         d.bias = nullptr;
         d.noise = d.noise_w = nullptr;
@@ -1265,34 +1269,35 @@ static int conv_launch(const float *x, const float *w, const float *in_scale, co
     }
     int rc = check_launch("g2s_modconv");
     if (rc != G2S_OK || !deferred_epilogue) return rc;
-    if (noise) {    // StyledConv tail in place (bias is required there, act = leaky-ReLU)
-        G2S_REQUIRE(bias && act == 1, "noise epilogue: needs a bias and act = 1");
-        return g2s_noise_bias_act(y, noise, noise_w, bias, y, B, d.My, d.OHf * d.OWf, act_alpha, act_gain, stream);
+    if (ep.noise) {    // StyledConv tail in place (bias is required there, act = leaky-ReLU)
+        G2S_REQUIRE(ep.bias && ep.act == 1, "noise epilogue: needs a bias and act = 1");
+        return g2s_noise_bias_act(y, ep.noise, ep.noise_w, ep.bias, y, B, d.My, d.OHf * d.OWf, ep.alpha, ep.gain,
+                                  stream);
     }
-    return g2s_fused_bias_act(y, bias, nullptr, y, (int64_t)B * d.My * d.OHf * d.OWf,
-                              (int64_t)d.OHf * d.OWf, d.My, act ? 3 : 1, 0, act_alpha,
-                              act ? act_gain : 1.0f, G2S_F32, stream);
+    return g2s_fused_bias_act(y, ep.bias, nullptr, y, (int64_t)B * d.My * d.OHf * d.OWf,
+                              (int64_t)d.OHf * d.OWf, d.My, ep.act ? 3 : 1, 0, ep.alpha,
+                              ep.act ? ep.gain : 1.0f, G2S_F32, stream);
 }
 
 // The StyleGAN2 modes of g2s_modconv in terms of the general geometry (w is always [Cout, Cin, k, k]).
 static int modconv_launch(const float *x, const float *w, const float *in_scale,
-                          const float *out_scale, const float *bias, int act, float act_alpha,
-                          float act_gain, float *y, int B, int Cin, int Cout, int H, int W, int k,
-                          int mode, int transpose, g2s_stream_t stream, bool f16_operands = false,
+                          const float *out_scale, const Epilogue &ep, float *y, int B, int Cin, int Cout, int H,
+                          int W, int k, int mode, int transpose, g2s_stream_t stream, bool f16_operands = false,
                           bool y_is_zero = false, int *plan_needs_zero = nullptr) {
     G2S_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "sizes must be positive");
     G2S_REQUIRE(k == 1 || k == 3, "kernel size must be 1 or 3 (got %d)", k);
     G2S_REQUIRE(mode == G2S_CONV_PLAIN || mode == G2S_CONV_UP2 || mode == G2S_CONV_DOWN2,
                 "unsupported mode %d", mode);
     // fromRGB (1x1 from 3 channels over >= 64 K pixels) runs as a streaming kernel (thinconv.hip) instead
-    // of an MFMA tile whose K is padding.  A forced tile keeps the call on the MFMA kernel (tests).
-    if (!f16_operands && !in_scale && !out_scale && mode == G2S_CONV_PLAIN && g_force_tile == -1 &&
+    // of an MFMA tile whose K is padding; that kernel has no noise term.  A forced tile keeps the call on the
+    // MFMA kernel (tests).
+    if (!f16_operands && !in_scale && !out_scale && !ep.noise && mode == G2S_CONV_PLAIN && g_force_tile == -1 &&
         g_force_splitk == -1 && thin_conv_eligible(B, Cin, Cout, H, W, k, transpose)) {
         if (plan_needs_zero) {
             *plan_needs_zero = 0;
             return G2S_OK;
         }
-        return thin_conv_launch(x, w, bias, y, B, Cin, Cout, H, W, act, act_alpha, act_gain, stream);
+        return thin_conv_launch(x, w, ep.bias, y, B, Cin, Cout, H, W, ep.act, ep.alpha, ep.gain, stream);
     }
     ConvGeom g{};
     g.k = k;
@@ -1308,14 +1313,13 @@ static int modconv_launch(const float *x, const float *w, const float *in_scale,
         for (int pass = 0; pass < 2 && tile == -1 && splitk == -1; pass++)   // pass 1: the row measured without / with the epilogue
             for (const TunedConv *t = kTuned; t->B; ++t)
                 if (t->B == B && t->Cin == Cin && t->Cout == Cout && t->H == H && t->k == k && t->mode == mode &&
-                    t->transpose == transpose && (pass == 1 || t->fused == (bias != nullptr || act != 0))) {
+                    t->transpose == transpose && (pass == 1 || t->fused == (ep.bias != nullptr || ep.act != 0))) {
                     tile = t->tile;
                     splitk = t->splitk;
                     break;
                 }
-    return conv_launch(x, w, in_scale, out_scale, bias, act, act_alpha, act_gain, y, B,
-                       transpose ? Cout : Cin, transpose ? Cin : Cout, H, W, g, tile, splitk, stream, y_is_zero,
-                       f16_operands, 1, nullptr, plan_needs_zero);
+    return conv_launch(x, w, in_scale, out_scale, ep, y, B, transpose ? Cout : Cin, transpose ? Cin : Cout, H, W, g,
+                       tile, splitk, stream, y_is_zero, f16_operands, 1, nullptr, plan_needs_zero);
 }
 
 // g2s_modconv + g2s_conv_bias_act in one entry point, with the caller's promise that y is already
@@ -1325,8 +1329,8 @@ extern "C" int g2s_modconv_ex(const float *x, const float *w, const float *in_sc
                               const float *bias, float *y, int B, int Cin, int Cout, int H, int W, int k, int mode,
                               int transpose, int act, float alpha, float gain, int y_is_zero, g2s_stream_t stream) {
     G2S_REQUIRE(act == 0 || act == 1, "act must be 0 (none) or 1 (leaky-ReLU)");
-    return modconv_launch(x, w, in_scale, out_scale, bias, act, alpha, gain, y, B, Cin, Cout, H, W, k, mode,
-                          transpose, stream, false, y_is_zero != 0);
+    return modconv_launch(x, w, in_scale, out_scale, Epilogue{bias, nullptr, nullptr, act, alpha, gain}, y, B, Cin,
+                          Cout, H, W, k, mode, transpose, stream, false, y_is_zero != 0);
 }
 
 // g2s_modconv_ex with the whole StyledConv tail (stylegan2-pytorch/model.py:349-355) in the epilogue:
@@ -1336,12 +1340,8 @@ extern "C" int g2s_modconv_nba(const float *x, const float *w, const float *in_s
                                int Cout, int H, int W, int k, int mode, int transpose, float alpha, float gain,
                                int y_is_zero, g2s_stream_t stream) {
     G2S_REQUIRE(bias && noise && noise_w, "bias, noise and noise_w must not be NULL");
-    t_noise = noise;
-    t_noise_w = noise_w;
-    const int rc = modconv_launch(x, w, in_scale, out_scale, bias, 1, alpha, gain, y, B, Cin, Cout, H, W, k, mode,
-                                  transpose, stream, false, y_is_zero != 0);
-    t_noise = t_noise_w = nullptr;
-    return rc;
+    return modconv_launch(x, w, in_scale, out_scale, Epilogue{bias, noise, noise_w, 1, alpha, gain}, y, B, Cin, Cout,
+                          H, W, k, mode, transpose, stream, false, y_is_zero != 0);
 }
 
 // 1 if that launch adds into a cleared output (split-K slices / polyphase holes), else 0; < 0: error.
@@ -1350,8 +1350,9 @@ extern "C" int g2s_modconv_needs_zero(int B, int Cin, int Cout, int H, int W, in
     int needs = 0;
     static const float dummy = 0.0f;   // never dereferenced: the plan mode launches nothing
     const float *sc = has_scales ? &dummy : nullptr;
-    const int rc = modconv_launch(nullptr, nullptr, sc, nullptr, fused ? &dummy : nullptr, fused ? 1 : 0, 0.0f, 1.0f,
-                                  nullptr, B, Cin, Cout, H, W, k, mode, transpose, nullptr, false, false, &needs);
+    const Epilogue ep{fused ? &dummy : nullptr, nullptr, nullptr, fused ? 1 : 0, 0.0f, 1.0f};
+    const int rc = modconv_launch(nullptr, nullptr, sc, nullptr, ep, nullptr, B, Cin, Cout, H, W, k, mode, transpose,
+                                  nullptr, false, false, &needs);
     return rc == G2S_OK ? needs : rc;
 }
 
@@ -1359,23 +1360,22 @@ extern "C" int g2s_modconv_f16(const float *x, const float *w, const float *in_s
                                const float *bias, float *y, int B, int Cin, int Cout, int H, int W, int k,
                                int mode, int transpose, int act, float alpha, float gain, g2s_stream_t stream) {
     G2S_REQUIRE(act == 0 || act == 1, "act must be 0 (none) or 1 (leaky-ReLU)");
-    return modconv_launch(x, w, in_scale, out_scale, bias, act, alpha, gain, y, B, Cin, Cout, H, W, k, mode,
-                          transpose, stream, true);
+    return modconv_launch(x, w, in_scale, out_scale, Epilogue{bias, nullptr, nullptr, act, alpha, gain}, y, B, Cin,
+                          Cout, H, W, k, mode, transpose, stream, true);
 }
 
 extern "C" int g2s_modconv(const float *x, const float *w, const float *in_scale,
                            const float *out_scale, float *y, int B, int Cin, int Cout, int H, int W,
                            int k, int mode, int transpose, g2s_stream_t stream) {
-    return modconv_launch(x, w, in_scale, out_scale, nullptr, 0, 0.0f, 1.0f, y, B, Cin, Cout, H, W, k,
-                          mode, transpose, stream);
+    return modconv_launch(x, w, in_scale, out_scale, kNoEpilogue, y, B, Cin, Cout, H, W, k, mode, transpose, stream);
 }
 
 extern "C" int g2s_conv_bias_act(const float *x, const float *w, const float *bias, float *y, int B,
                                  int Cin, int Cout, int H, int W, int k, int mode, int act,
                                  float alpha, float gain, g2s_stream_t stream) {
     G2S_REQUIRE(act == 0 || act == 1, "act must be 0 (none) or 1 (leaky-ReLU)");
-    return modconv_launch(x, w, nullptr, nullptr, bias, act, alpha, gain, y, B, Cin, Cout, H, W, k,
-                          mode, 0, stream);
+    return modconv_launch(x, w, nullptr, nullptr, Epilogue{bias, nullptr, nullptr, act, alpha, gain}, y, B, Cin, Cout,
+                          H, W, k, mode, 0, stream);
 }
 
 static int conv2d_impl(const float *x, const float *w, const float *bias, float *y, int B, int Cr, int M, int H,
@@ -1394,8 +1394,8 @@ static int conv2d_impl(const float *x, const float *w, const float *bias, float 
                 splitk = t->splitk;
                 break;
             }
-    return conv_launch(x, w, nullptr, nullptr, bias, act, alpha, gain, y, B, Cr, M, H, W, g, tile, splitk, stream,
-                       y_is_zero != 0, false, groups, rider);
+    return conv_launch(x, w, nullptr, nullptr, Epilogue{bias, nullptr, nullptr, act, alpha, gain}, y, B, Cr, M, H, W,
+                       g, tile, splitk, stream, y_is_zero != 0, false, groups, rider);
 }
 
 extern "C" int g2s_conv2d(const float *x, const float *w, const float *bias, float *y, int B, int Cr,

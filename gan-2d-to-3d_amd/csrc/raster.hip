@@ -712,7 +712,8 @@ extern "C" int g2s_raster_depth_bwd_ex(const float *verts, const int32_t *faces,
                                        const float *grad_depth, const int32_t *face_idx,
                                        const float *bary, int B, int n_verts, int n_faces, int S,
                                        const float *K, float orig_size, int ssaa, float *grad_verts,
-                                       void *workspace, size_t workspace_bytes, g2s_stream_t stream) {
+                                       void *workspace, size_t workspace_bytes, int acc_is_zero,
+                                       g2s_stream_t stream) {
     G2S_REQUIRE(verts && grad_depth && face_idx && bary && grad_verts, "NULL pointer argument");
     int rc = check_shape(faces, B, n_verts, n_faces, S, ssaa);
     if (rc) return rc;
@@ -740,11 +741,11 @@ extern "C" int g2s_raster_depth_bwd_ex(const float *verts, const int32_t *faces,
                         "(g2s_raster_bwd_workspace_bytes = %zu bytes, got %zu)",
                         g2s_raster_bwd_workspace_bytes(B, n_verts), workspace ? workspace_bytes : (size_t)0);
         p.gfix = reinterpret_cast<long long *>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-        if (!precleared() && hipMemsetAsync(p.gfix, 0, (size_t)B * n_verts * 3 * sizeof(long long), st) != hipSuccess)
+        if (!acc_is_zero && hipMemsetAsync(p.gfix, 0, (size_t)B * n_verts * 3 * sizeof(long long), st) != hipSuccess)
             return fail(G2S_ERR_LAUNCH, "hipMemsetAsync(workspace) failed");
         raster_bwd_samples<long long><<<dim3(cdiv(bw_tiles, 4), B), 256, 0, st>>>(p);
     } else {
-        if (!precleared() && hipMemsetAsync(grad_verts, 0, (size_t)B * n_verts * 3 * sizeof(float), st) != hipSuccess)
+        if (!acc_is_zero && hipMemsetAsync(grad_verts, 0, (size_t)B * n_verts * 3 * sizeof(float), st) != hipSuccess)
             return fail(G2S_ERR_LAUNCH, "hipMemsetAsync(grad_verts) failed");
         raster_bwd_samples<float><<<dim3(cdiv(bw_tiles, 4), B), 256, 0, st>>>(p);
     }
@@ -758,5 +759,5 @@ extern "C" int g2s_raster_depth_bwd(const float *verts, const int32_t *faces,
                                     const float *K, float orig_size, int ssaa, float *grad_verts,
                                     g2s_stream_t stream) {
     return g2s_raster_depth_bwd_ex(verts, faces, grad_depth, face_idx, bary, B, n_verts, n_faces, S, K,
-                                   orig_size, ssaa, grad_verts, nullptr, 0, stream);
+                                   orig_size, ssaa, grad_verts, nullptr, 0, 0, stream);
 }

@@ -13,7 +13,7 @@ from . import zeropool as _zp
 
 def _cleared(shape, device):
     """(tensor, from_pool): an accumulator the library call would otherwise clear with a memset of its own — a
-    slice of the step's cleared pool when one is active (then the call runs under lib.precleared), else plain
+    slice of the step's cleared pool when one is active (then the call is told so, acc_is_zero = 1), else plain
     memory that the call clears itself."""
     t = _zp.take(tuple(shape), device)
     if t is not None:
@@ -78,10 +78,9 @@ class WarpVertsFunction(Function):
         gdepth = torch.empty_like(depth)
         grt, pre = _cleared((B, 12), depth.device) if need_rt else (None, False)
         L = _lib.load()
-        with _lib.precleared(pre):
-            _lib.check(L.g2s_warp_verts_bwd(_lib.ptr(depth), _lib.ptr(rays), _lib.ptr(R),
-                                            _lib.ptr(_f32c(gverts)), ctx.rcd, _lib.ptr(gdepth),
-                                            _lib.ptr(grt), B, H * W, _lib.stream()))
+        _lib.check(L.g2s_warp_verts_bwd(_lib.ptr(depth), _lib.ptr(rays), _lib.ptr(R),
+                                        _lib.ptr(_f32c(gverts)), ctx.rcd, _lib.ptr(gdepth),
+                                        _lib.ptr(grt), B, H * W, int(pre), _lib.stream()))
         gR = grt[:, :9].reshape(B, 3, 3) if need_rt else None
         gt = grt[:, 9:].reshape(B, 1, 3) if need_rt else None
         return gdepth, None, gR, gt, None
@@ -114,10 +113,9 @@ class InvWarpGridFunction(Function):
         grt, pre = _cleared((B, 12), depth.device) if need_rt else (None, False)
         Kc = (_lib.C.c_float * 9)(*K9)
         L = _lib.load()
-        with _lib.precleared(pre):
-            _lib.check(L.g2s_inv_warp_grid_bwd(_lib.ptr(depth), _lib.ptr(rays), _lib.ptr(R), _lib.ptr(t),
-                                               Kc, rcd, _lib.ptr(_f32c(ggrid)), _lib.ptr(gdepth),
-                                               _lib.ptr(grt), B, H, W, _lib.stream()))
+        _lib.check(L.g2s_inv_warp_grid_bwd(_lib.ptr(depth), _lib.ptr(rays), _lib.ptr(R), _lib.ptr(t),
+                                           Kc, rcd, _lib.ptr(_f32c(ggrid)), _lib.ptr(gdepth),
+                                           _lib.ptr(grt), B, H, W, int(pre), _lib.stream()))
         gR = grt[:, :9].reshape(B, 3, 3) if need_rt else None
         gt = grt[:, 9:].reshape(B, 1, 3) if need_rt else None
         return gdepth, None, gR, gt, None, None
@@ -132,8 +130,7 @@ class SmoothLossFunction(Function):
         N, H, W = p.shape
         loss, pre = _cleared((), p.device)
         L = _lib.load()
-        with _lib.precleared(pre):
-            _lib.check(L.g2s_smooth_loss_fwd(_lib.ptr(p), _lib.ptr(loss), N, H, W, _lib.stream()))
+        _lib.check(L.g2s_smooth_loss_fwd(_lib.ptr(p), _lib.ptr(loss), N, H, W, int(pre), _lib.stream()))
         ctx.save_for_backward(p)
         ctx.shape = pred.shape
         return loss
@@ -207,10 +204,9 @@ class ShadingFunction(Function):
         glight, pre = _cleared((B, 4), dev)
         gd = None if gdiffuse is None else _f32c(gdiffuse)
         L = _lib.load()
-        with _lib.precleared(pre):
-            _lib.check(L.g2s_shading_bwd(_lib.ptr(normal), _lib.ptr(light), _lib.ptr(albedo), _lib.ptr(gd),
-                                         _lib.ptr(_f32c(gtexture)), _lib.ptr(gnormal), _lib.ptr(galbedo),
-                                         _lib.ptr(glight), B, Bn, Ba, H * W, _lib.stream()))
+        _lib.check(L.g2s_shading_bwd(_lib.ptr(normal), _lib.ptr(light), _lib.ptr(albedo), _lib.ptr(gd),
+                                     _lib.ptr(_f32c(gtexture)), _lib.ptr(gnormal), _lib.ptr(galbedo),
+                                     _lib.ptr(glight), B, Bn, Ba, H * W, int(pre), _lib.stream()))
         if Bn == 1 and B > 1:
             gnormal = gnormal.sum(0, keepdim=True)
         if Ba == 1 and B > 1:
@@ -242,9 +238,8 @@ class DepthHeadFunction(Function):
         raw, mean = ctx.saved_tensors
         g_raw = torch.empty_like(raw)
         gsum, pre = _cleared((1,), raw.device)
-        with _lib.precleared(pre):
-            _lib.check(_lib.load().g2s_depth_head_bwd(_lib.ptr(raw), _lib.ptr(mean), _lib.ptr(_f32c(g)), _lib.ptr(g_raw),
-                                                      _lib.ptr(gsum), *ctx.args, _lib.stream()))
+        _lib.check(_lib.load().g2s_depth_head_bwd(_lib.ptr(raw), _lib.ptr(mean), _lib.ptr(_f32c(g)), _lib.ptr(g_raw),
+                                                  _lib.ptr(gsum), *ctx.args, int(pre), _lib.stream()))
         return g_raw, None, None, None, None, None
 
 

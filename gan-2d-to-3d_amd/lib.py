@@ -23,19 +23,18 @@ SIGNATURES = {
     "g2s_res_split_fwd": (_i, [_p, _p, _p, _i64, _i, _i, _p]),
     "g2s_res_split_bwd": (_i, [_p, _p, _p, _p, _i64, _i, _i, _p]),
     "g2s_depth_head_fwd": (_i, [_p, _p, _p, _i64, _i, _f, _f, _i, _f, _p]),
-    "g2s_depth_head_bwd": (_i, [_p, _p, _p, _p, _p, _i64, _i, _f, _f, _i, _f, _p]),
+    "g2s_depth_head_bwd": (_i, [_p, _p, _p, _p, _p, _i64, _i, _f, _f, _i, _f, _i, _p]),
     "g2s_grid_sample_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _f, _p]),
     "g2s_grid_sample_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "g2s_grid_sample_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _f, _p, _sz, _p]),
+    "g2s_grid_sample_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _f, _p, _sz, _i, _p]),
     "g2s_set_deterministic": (_i, [_i]),
     "g2s_get_deterministic": (_i, []),
-    "g2s_set_precleared": (_i, [_i]),
     "g2s_raster_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "g2s_raster_tune": (_i, [_i]),
     "g2s_raster_depth_fwd": (_i, [_p, _p, _i, _i, _i, _i, _p, _f, _i, _i, _f, _f, _p, _p, _p, _p, _sz, _p]),
     "g2s_raster_depth_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _f, _i, _p, _p]),
     "g2s_raster_bwd_workspace_bytes": (_sz, [_i, _i]),
-    "g2s_raster_depth_bwd_ex": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _f, _i, _p, _p, _sz, _p]),
+    "g2s_raster_depth_bwd_ex": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _f, _i, _p, _p, _sz, _i, _p]),
     "g2s_raster_rgb_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _f, _p, _p]),
     "g2s_fused_bias_act": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i, _i, _f, _f, _i, _p]),
     "g2s_maxpool2x2_fwd": (_i, [_p, _p, _i64, _i, _i, _p]),
@@ -87,14 +86,14 @@ SIGNATURES = {
     "g2s_view_transform_fwd": (_i, [_p, _f, _f, _f, _p, _p, _i, _p]),
     "g2s_view_transform_bwd": (_i, [_p, _f, _f, _f, _p, _p, _p, _i, _p]),
     "g2s_warp_verts_fwd": (_i, [_p, _p, _p, _p, _f, _p, _i, _i, _p]),
-    "g2s_warp_verts_bwd": (_i, [_p, _p, _p, _p, _f, _p, _p, _i, _i, _p]),
+    "g2s_warp_verts_bwd": (_i, [_p, _p, _p, _p, _f, _p, _p, _i, _i, _i, _p]),
     "g2s_inv_warp_grid_fwd": (_i, [_p, _p, _p, _p, _p, _f, _p, _i, _i, _i, _p]),
-    "g2s_inv_warp_grid_bwd": (_i, [_p, _p, _p, _p, _p, _f, _p, _p, _p, _i, _i, _i, _p]),
+    "g2s_inv_warp_grid_bwd": (_i, [_p, _p, _p, _p, _p, _f, _p, _p, _p, _i, _i, _i, _i, _p]),
     "g2s_normal_fwd": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "g2s_normal_bwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "g2s_shading_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
-    "g2s_shading_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
-    "g2s_smooth_loss_fwd": (_i, [_p, _p, _i, _i, _i, _p]),
+    "g2s_shading_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "g2s_smooth_loss_fwd": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "g2s_smooth_loss_bwd": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "g2s_groupnorm_workspace_floats": (_sz, [_i, _i, _i, _i]),
     "g2s_groupnorm_act_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _f, _p]),
@@ -132,23 +131,6 @@ def set_deterministic(on=True):
     prev = bool(L.g2s_get_deterministic())
     check(L.g2s_set_deterministic(int(bool(on))))
     return prev
-
-
-class precleared:
-    """with precleared(on): <one library call> — g2s_set_precleared around the call: the accumulators that call
-    would clear itself come from the step's cleared pool (zeropool.take) and its memsets are skipped."""
-
-    def __init__(self, on=True):
-        self.on = bool(on)
-
-    def __enter__(self):
-        if self.on:
-            self.prev = load().g2s_set_precleared(1)
-
-    def __exit__(self, *exc):
-        if self.on:
-            load().g2s_set_precleared(self.prev)
-        return False
 
 
 def check(rc):

@@ -46,9 +46,8 @@ class _GridSample(Function):
             pre = gx is not None
             if gx is None:
                 gx = torch.empty_like(x)
-        with _lib.precleared(pre):
-            _lib.check(L.g2s_grid_sample_bwd(_lib.ptr(gy.contiguous()), _lib.ptr(x), _lib.ptr(grid), _lib.ptr(gx), _lib.ptr(gg),
-                                             *ctx.args, _lib.ptr(ws), ws_bytes, _lib.stream()))
+        _lib.check(L.g2s_grid_sample_bwd(_lib.ptr(gy.contiguous()), _lib.ptr(x), _lib.ptr(grid), _lib.ptr(gx), _lib.ptr(gg),
+                                         *ctx.args, _lib.ptr(ws), ws_bytes, int(pre), _lib.stream()))
         return gx, gg, None, None
 
 

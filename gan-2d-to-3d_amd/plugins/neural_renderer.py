@@ -93,7 +93,7 @@ class RenderDepthFunction(Function):
         Kc = (_lib.C.c_float * 9)(*K)
         # the scatter target must start at zero — default mode: the gradient itself; deterministic mode: the
         # fixed-point scratch buffer (include/g2s.h).  A slice of the step's cleared pool when there is one
-        # (the call then runs under lib.precleared), else the call clears it with a memset of its own.
+        # (the call is then told so, acc_is_zero = 1), else the call clears it with a memset of its own.
         ws, ws_bytes, pre = None, 0, False
         if L.g2s_get_deterministic():
             ws_bytes = L.g2s_raster_bwd_workspace_bytes(B, N)
@@ -107,10 +107,9 @@ class RenderDepthFunction(Function):
             pre = gv is not None
             if gv is None:
                 gv = torch.empty_like(verts)
-        with _lib.precleared(pre):
-            _lib.check(L.g2s_raster_depth_bwd_ex(_lib.ptr(verts), _lib.ptr(faces), _lib.ptr(g),
-                                                 _lib.ptr(fidx), _lib.ptr(bary), B, N, F, S, Kc, orig_size,
-                                                 ssaa, _lib.ptr(gv), _lib.ptr(ws), ws_bytes, _lib.stream()))
+        _lib.check(L.g2s_raster_depth_bwd_ex(_lib.ptr(verts), _lib.ptr(faces), _lib.ptr(g),
+                                             _lib.ptr(fidx), _lib.ptr(bary), B, N, F, S, Kc, orig_size,
+                                             ssaa, _lib.ptr(gv), _lib.ptr(ws), ws_bytes, int(pre), _lib.stream()))
         return gv, None, None, None, None, None, None, None, None
 
 

@@ -10,10 +10,9 @@
  *     never synchronises, never throws);
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream);
  *   - returns G2S_OK (0) or a negative error code; g2s_last_error() gives a thread-local message;
- *   - re-entrant.  Thread-local state: the error string, the two tuning overrides
+ *   - re-entrant.  Thread-local state: the error string and the two tuning overrides
  *     g2s_modconv_tune / g2s_raster_tune (off by default; they select among launch configurations
- *     that produce the same results, and only affect the calling thread) and g2s_set_precleared
- *     (off by default: the caller has cleared the accumulators of the next call).  Process-global state:
+ *     that produce the same results, and only affect the calling thread).  Process-global state:
  *     ONE flag, g2s_set_deterministic (off by default).  No environment variable is read.
  */
 #ifndef G2S_H
@@ -54,14 +53,13 @@ const char *g2s_last_error(void);
 int g2s_set_deterministic(int on);
 int g2s_get_deterministic(void);
 
-/* Caller-cleared accumulators (no reference counterpart; per THREAD, returns the previous value).  The backward
- * functions below that accumulate into small outputs or workspaces clear them first with a memset of their own —
- * one more launch each (14 of step 3's).  While this flag is on, the calling thread guarantees that those buffers
- * are already zero (the Python side carves them from the step's one cleared pool, zeropool.py) and the memsets are
- * skipped: g2s_warp_verts_bwd / g2s_inv_warp_grid_bwd (gRt), g2s_smooth_loss_fwd (loss), g2s_shading_bwd (glight),
+/* Caller-cleared accumulators (no reference counterpart).  The functions below that accumulate into small outputs
+ * or workspaces clear them first with a memset of their own — one more launch each (14 of step 3's).  With
+ * acc_is_zero = 1 the caller guarantees that the buffer the call adds into is already zero (the Python side carves
+ * them from the step's one cleared pool, zeropool.py) and the memset is skipped; it holds for that call only:
+ * g2s_warp_verts_bwd / g2s_inv_warp_grid_bwd (gRt), g2s_smooth_loss_fwd (loss), g2s_shading_bwd (glight),
  * g2s_depth_head_bwd (gsum), g2s_grid_sample_bwd (gx, or the deterministic mode's fixed-point workspace),
- * g2s_raster_depth_bwd(_ex) (grad_verts, or its fixed-point workspace).  Set it around ONE call and restore it. */
-int g2s_set_precleared(int on);
+ * g2s_raster_depth_bwd_ex (grad_verts, or its fixed-point workspace; g2s_raster_depth_bwd passes 0). */
 
 /* ------------------------------------------------------------------------------------------
  * Differentiable depth rasterizer.
@@ -114,12 +112,13 @@ int g2s_raster_depth_bwd(const float *verts, const int32_t *faces, const float *
  * on the order the tiles arrive in — the gradient is bit-identical from run to run — and converted to
  * grad_verts at the end (range +-8.4e6 per component, resolution 9e-13; non-finite contributions are
  * dropped).  In deterministic mode a NULL / short workspace is G2S_ERR_WORKSPACE — also through
- * g2s_raster_depth_bwd, which passes none; otherwise the workspace is ignored. */
+ * g2s_raster_depth_bwd, which passes none; otherwise the workspace is ignored.  acc_is_zero = 1: the buffer the
+ * sums go to (the workspace in deterministic mode, else grad_verts) is already zero, no memset. */
 size_t g2s_raster_bwd_workspace_bytes(int B, int n_verts);
 int g2s_raster_depth_bwd_ex(const float *verts, const int32_t *faces, const float *grad_depth,
                             const int32_t *face_idx, const float *bary, int B, int n_verts,
                             int n_faces, int S, const float *K, float orig_size, int ssaa,
-                            float *grad_verts, void *workspace, size_t workspace_bytes,
+                            float *grad_verts, void *workspace, size_t workspace_bytes, int acc_is_zero,
                             g2s_stream_t stream);
 
 /* Texture path: nr.Renderer.render_rgb(vertices, faces, textures [B,F,ts,ts,ts,C]) as the reference's
@@ -180,28 +179,31 @@ int g2s_res_split_bwd(const float *x, const float *g_relu, const float *g_pool, 
  * clamp_border: out = d * (1 - b) + b * border_depth with b = 1.02 in the two left / right columns of every
  * row of W, else 0.  mean: device float (the whole-batch mean of raw, reduced by the caller — under data
  * parallelism the all-reduced one).  _bwd: g_raw = gc - mean(gc), gc = g * d out / d (raw - mean) — the
- * centring's own backward included (mean taken over these n elements); gsum: one device float of scratch. */
+ * centring's own backward included (mean taken over these n elements); gsum: one device float of scratch
+ * (acc_is_zero = 1: already zero, no memset). */
 int g2s_depth_head_fwd(const float *raw, const float *mean, float *out, int64_t n, int W, float lo, float hi,
                        int clamp_border, float border_depth, g2s_stream_t stream);
 int g2s_depth_head_bwd(const float *raw, const float *mean, const float *g, float *g_raw, float *gsum, int64_t n,
-                       int W, float lo, float hi, int clamp_border, float border_depth, g2s_stream_t stream);
+                       int W, float lo, float hi, int clamp_border, float border_depth, int acc_is_zero,
+                       g2s_stream_t stream);
 
 /* The reconstruction warp: torch.nn.functional.grid_sample(x, grid, mode='bilinear', padding_mode='zeros',
  * align_corners=True) as GAN2Shape/model.py:147,267 calls it, optionally followed by .clamp(lo, hi)
  * (model.py:150,270) in the same pass (clamp = 1).  ATen's arithmetic (corner order nw, ne, sw, se).
  *   x [B, C, IH, IW], grid [B, H, W, 2] (x then y in [-1, 1]), y / gy [B, C, H, W], all f32.
- * Backward: gx [B, C, IH, IW] (zero-filled by the callee, then scattered) and ggrid [B, H, W, 2]; either
- * may be NULL.  With clamp = 1 the gradient passes where lo <= sample <= hi (torch's rule), the sample
- * being recomputed.  The scatter uses float atomics; in deterministic mode (g2s_set_deterministic) it
- * accumulates 2^-40 fixed point with 64-bit integer atomics in `workspace`
+ * Backward: gx [B, C, IH, IW] (zero-filled by the callee unless acc_is_zero = 1, then scattered) and
+ * ggrid [B, H, W, 2]; either may be NULL.  With clamp = 1 the gradient passes where lo <= sample <= hi
+ * (torch's rule), the sample being recomputed.  The scatter uses float atomics; in deterministic mode
+ * (g2s_set_deterministic) it accumulates 2^-40 fixed point with 64-bit integer atomics in `workspace`
  * (>= g2s_grid_sample_bwd_workspace_bytes) and converts at the end — bit-identical from run to run, which
- * ATen's grid_sampler_2d_backward cannot offer; there a NULL / short workspace is G2S_ERR_WORKSPACE. */
+ * ATen's grid_sampler_2d_backward cannot offer; there a NULL / short workspace is G2S_ERR_WORKSPACE, and
+ * acc_is_zero = 1 promises a cleared workspace instead of a cleared gx. */
 int g2s_grid_sample_fwd(const float *x, const float *grid, float *y, int B, int C, int IH, int IW, int H, int W,
                         int clamp, float lo, float hi, g2s_stream_t stream);
 size_t g2s_grid_sample_bwd_workspace_bytes(int B, int C, int IH, int IW);
 int g2s_grid_sample_bwd(const float *gy, const float *x, const float *grid, float *gx, float *ggrid, int B, int C,
                         int IH, int IW, int H, int W, int clamp, float lo, float hi, void *workspace,
-                        size_t workspace_bytes, g2s_stream_t stream);
+                        size_t workspace_bytes, int acc_is_zero, g2s_stream_t stream);
 
 /* torch.clamp(x, lo, hi) of the step's image / depth clamps (GAN2Shape/model.py:150,270, renderer.py:123-124)
  * and its backward as ONE launch each (autograd's ClampBackward is five: ge, le, logical_and, where, fill).
@@ -559,7 +561,8 @@ int g2s_weighted_l1_bwd3(const float *x, const float *y, const float *w, const f
  *   g2s_inv_warp_grid_*   grid [B,H,W,2] = normalise(K (R^T (d ray - t - c) + c))  (renderer.py:97-114)
  *   g2s_smooth_loss_*     mean|dx2| + mean|dxdy| + mean|dydx| + mean|dy2| of p [N,H,W]  (losses.py:54-79)
  * Backward entry points write gdepth / gview / gp fully; gRt [B,12] (9 of R, 3 of t; may be NULL)
- * is zero-filled by the callee then accumulated with one float atomic per workgroup.
+ * is zero-filled by the callee (unless acc_is_zero = 1: already zero) then accumulated with one float atomic per
+ * workgroup; so is the smoothness loss (one device float).
  * ---------------------------------------------------------------------------------------- */
 int g2s_view_transform_fwd(const float *view, float rot_scale, float txy_scale, float tz_scale,
                            float *R, float *t, int B, g2s_stream_t stream);
@@ -568,18 +571,19 @@ int g2s_view_transform_bwd(const float *view, float rot_scale, float txy_scale, 
 int g2s_warp_verts_fwd(const float *depth, const float *rays, const float *R, const float *t,
                        float rot_center_depth, float *verts, int B, int P, g2s_stream_t stream);
 int g2s_warp_verts_bwd(const float *depth, const float *rays, const float *R, const float *gverts,
-                       float rot_center_depth, float *gdepth, float *gRt, int B, int P,
+                       float rot_center_depth, float *gdepth, float *gRt, int B, int P, int acc_is_zero,
                        g2s_stream_t stream);
 int g2s_inv_warp_grid_fwd(const float *depth, const float *rays, const float *R, const float *t,
                           const float *K, float rot_center_depth, float *grid, int B, int H, int W,
                           g2s_stream_t stream);
 int g2s_inv_warp_grid_bwd(const float *depth, const float *rays, const float *R, const float *t,
                           const float *K, float rot_center_depth, const float *ggrid, float *gdepth,
-                          float *gRt, int B, int H, int W, g2s_stream_t stream);
+                          float *gRt, int B, int H, int W, int acc_is_zero, g2s_stream_t stream);
 /*   g2s_normal_*      normal [B,H,W,3] from depth (renderer.py:127-139), gradient to depth
  *   g2s_shading_*     light [B,4] (a, b, dx, dy raw), normal [Bn,H,W,3], albedo [Ba,3,H,W] (Bn, Ba in
  *                     {1, B}) -> diffuse [B,1,H,W], texture [B,3,H,W] (model.py:347-360); backward
- *                     writes per-sample gnormal [B,H,W,3], galbedo [B,3,H,W] and glight [B,4]. */
+ *                     writes per-sample gnormal [B,H,W,3], galbedo [B,3,H,W] and adds into glight [B,4],
+ *                     which it clears first unless acc_is_zero = 1. */
 int g2s_normal_fwd(const float *depth, const float *rays, float *normal, int B, int H, int W,
                    g2s_stream_t stream);
 int g2s_normal_bwd(const float *depth, const float *rays, const float *gnormal, float *gdepth, int B,
@@ -588,8 +592,8 @@ int g2s_shading_fwd(const float *normal, const float *light, const float *albedo
                     float *texture, int B, int Bn, int Ba, int P, g2s_stream_t stream);
 int g2s_shading_bwd(const float *normal, const float *light, const float *albedo,
                     const float *gdiffuse, const float *gtexture, float *gnormal, float *galbedo,
-                    float *glight, int B, int Bn, int Ba, int P, g2s_stream_t stream);
-int g2s_smooth_loss_fwd(const float *p, float *loss, int N, int H, int W, g2s_stream_t stream);
+                    float *glight, int B, int Bn, int Ba, int P, int acc_is_zero, g2s_stream_t stream);
+int g2s_smooth_loss_fwd(const float *p, float *loss, int N, int H, int W, int acc_is_zero, g2s_stream_t stream);
 int g2s_smooth_loss_bwd(const float *p, const float *gloss, float *gp, int N, int H, int W,
                         g2s_stream_t stream);
 

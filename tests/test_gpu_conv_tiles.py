@@ -463,6 +463,26 @@ def test_styledconv_tail_in_the_epilogue_vs_oracle(L, B, cin, cout, H):
         mc.WINOGRAD, mc.WINO_FORCE = saved
 
 
+def test_styledconv_tail_without_scales_keeps_the_noise(L):
+    """g2s_modconv_nba with NULL scales on a shape the thin 1x1 kernel takes (fromRGB-like: 3 -> 32 channels over
+    >= 64 K pixels): that kernel has no noise term, so the call must stay on the MFMA kernel, whose epilogue adds it."""
+    from gan2shape_amd import lib
+    B, cin, cout, H = 8, 3, 32, 128
+    rng = np.random.default_rng(11)
+    x = rng.standard_normal((B, cin, H, H)).astype(np.float32)
+    w = (rng.standard_normal((cout, cin, 1, 1)) / math.sqrt(cin)).astype(np.float32)
+    bias = rng.standard_normal(cout).astype(np.float32)
+    noise = rng.standard_normal((H, H)).astype(np.float32)
+    nw, alpha, gain = 0.37, 0.2, 2 ** 0.5
+    exp = _nba_expected(expected_modconv(x, w, None, None, PLAIN, 0), bias, noise, nw, alpha, gain)
+    xd, wd, bd, nd, nwd = dev(x), dev(w), dev(bias), dev(noise), dev(np.array([nw], np.float32))
+    y = torch.empty(B, cout, H, H, device="cuda")
+    L.g2s_modconv_tune(-1, -1)
+    lib.check(L.g2s_modconv_nba(lib.ptr(xd), lib.ptr(wd), None, None, lib.ptr(bd), lib.ptr(nd), lib.ptr(nwd),
+                                lib.ptr(y), B, cin, cout, H, H, 1, PLAIN, 0, alpha, gain, 0, lib.stream()))
+    _check(y, exp, cin, "StyledConv tail, NULL scales, thin-eligible shape")
+
+
 @pytest.mark.parametrize("B,C,H", [(8, 128, 129), (2, 512, 9), (3, 20, 35), (2, 8, 67)])
 def test_blur_with_the_styledconv_tail_vs_oracle(L, B, C, H):
     """g2s_upfirdn2d_nba: the Blur behind an up-sampling StyledConv's transposed convolution (model.py:264-275;

@@ -347,34 +347,88 @@ def test_channel_sum_is_the_bias_gradient(g2s):
         assert float((out.double() - ref).abs().max()) <= 1e-5 * max(1.0, float(ref.abs().max())), shape
 
 
-def test_precleared_skips_the_memset_and_the_pool_path_equals_the_plain_one(g2s):
-    """g2s_set_precleared (include/g2s.h): while the flag is on, g2s_shading_bwd adds into the caller's glight instead
-    of clearing it first (so a buffer prefilled with 1 comes back 1 too high — the memset is really skipped — and a
-    cleared one gives the plain result); the flag is per call (restored by lib.precleared); and the op-level wrappers
-    give bit-identical gradients with a step's zero pool active (accumulators carved from it) and without one."""
+def test_acc_is_zero_skips_the_memset_and_the_pool_path_equals_the_plain_one(g2s):
+    """acc_is_zero (include/g2s.h): with 1, a call adds into the caller's accumulator instead of clearing it first (so a
+    buffer prefilled with 1 comes back 1 too high — the memset is really skipped — and a cleared one gives the plain
+    result), for each of the seven entry points that take it; nothing carries over to the next call; and the op-level
+    wrappers give bit-identical gradients with a step's zero pool active (accumulators carved from it) and without one."""
     from gan2shape_amd import fused_geometry as fg, lib, zeropool
-    L = lib.load()
+    from gan2shape_amd.plugins import neural_renderer as nr
+    L, p, st = lib.load(), lib.ptr, lib.stream
     torch.manual_seed(3)
     B, H, W = 4, 16, 16
+    P = H * W
     normal = torch.nn.functional.normalize(torch.randn(B, H, W, 3, device="cuda"), dim=-1).contiguous()
     light = torch.randn(B, 4, device="cuda")
     albedo = torch.randn(B, 3, H, W, device="cuda")
     gd, gt = torch.randn(B, 1, H, W, device="cuda"), torch.randn(B, 3, H, W, device="cuda")
     gn, ga = torch.empty(B, H, W, 3, device="cuda"), torch.empty(B, 3, H, W, device="cuda")
+    depth = 1.0 + 0.1 * torch.rand(B, H, W, device="cuda")
+    rays = torch.cat([0.2 * torch.rand(P, 2, device="cuda") - 0.1, torch.ones(P, 1, device="cuda")], 1)
+    R = torch.eye(3, device="cuda") + 0.1 * torch.randn(B, 3, 3, device="cuda")
+    t = 0.1 * torch.randn(B, 3, device="cuda")
+    Kc = (lib.C.c_float * 9)(2.0 * W, 0.0, W / 2.0, 0.0, 2.0 * H, H / 2.0, 0.0, 0.0, 1.0)
+    gverts, ggrid = torch.randn(B, P, 3, device="cuda"), torch.randn(B, H, W, 2, device="cuda")
+    gdepth = torch.empty_like(depth)
+    g_head, g_raw = torch.randn(B * P, device="cuda"), torch.empty(B * P, device="cuda")
+    mean = depth.view(1, -1).mean(1)
+    x, gy = torch.randn(B, 3, H, W, device="cuda"), torch.randn(B, 3, H, W, device="cuda")
+    grid = 2 * torch.rand(B, H, W, 2, device="cuda") - 1
 
-    def call(glight, flag):
-        with lib.precleared(flag):
-            lib.check(L.g2s_shading_bwd(lib.ptr(normal), lib.ptr(light), lib.ptr(albedo), lib.ptr(gd), lib.ptr(gt),
-                                        lib.ptr(gn), lib.ptr(ga), lib.ptr(glight), B, B, B, H * W, lib.stream()))
-        return glight.clone()
+    def call(fn):
+        def run(acc, flag):
+            lib.check(fn(acc, flag))
+            return acc.clone()
+        return run
+    shading = call(lambda acc, flag: L.g2s_shading_bwd(p(normal), p(light), p(albedo), p(gd), p(gt), p(gn), p(ga),
+                                                        p(acc), B, B, B, P, flag, st()))
+    adders = {   # name: (accumulator shape, call)
+        "warp_verts gRt": ((B, 12), call(lambda acc, flag: L.g2s_warp_verts_bwd(
+            p(depth), p(rays), p(R), p(gverts), 0.9, p(gdepth), p(acc), B, P, flag, st()))),
+        "inv_warp_grid gRt": ((B, 12), call(lambda acc, flag: L.g2s_inv_warp_grid_bwd(
+            p(depth), p(rays), p(R), p(t), Kc, 0.9, p(ggrid), p(gdepth), p(acc), B, H, W, flag, st()))),
+        "smooth loss": ((), call(lambda acc, flag: L.g2s_smooth_loss_fwd(p(depth), p(acc), B, H, W, flag, st()))),
+        "shading glight": ((B, 4), shading),
+        "depth_head gsum": ((1,), call(lambda acc, flag: L.g2s_depth_head_bwd(
+            p(depth), p(mean), p(g_head), p(g_raw), p(acc), B * P, W, 0.9, 1.1, 1, 0.7, flag, st()))),
+        "grid_sample gx": ((B, 3, H, W), call(lambda acc, flag: L.g2s_grid_sample_bwd(
+            p(gy), p(x), p(grid), p(acc), None, B, 3, H, W, H, W, 0, 0.0, 0.0, None, 0, flag, st()))),
+    }
+    for name, (shape, fn) in adders.items():       # default mode: the sums are float atomics
+        plain = fn(torch.full(shape, 7.0, device="cuda"), 0)
+        dirty = fn(torch.ones(shape, device="cuda"), 1)                          # NOT cleared by anyone
+        assert float((dirty - plain - 1.0).abs().max()) <= 1e-5 * max(1.0, float(plain.abs().max())), name
+
+    # rasterizer backward: the scatter target is transformed in place afterwards, so only "cleared by the caller
+    # == cleared by the library" holds — bit for bit with the fixed-point workspace of deterministic mode
+    S = 32
+    ys, xs = torch.meshgrid(torch.linspace(-0.3, 0.3, S), torch.linspace(-0.3, 0.3, S), indexing="ij")
+    z = 1.0 + 0.05 * torch.randn(2, S, S).cumsum(1).cumsum(2) / S
+    verts = torch.stack([xs[None] * z, ys[None] * z, z], -1).reshape(2, S * S, 3).cuda().requires_grad_(True)
+    K = [2.0 * S, 0.0, S / 2.0, 0.0, 2.0 * S, S / 2.0, 0.0, 0.0, 1.0]
+    dep = nr.RenderDepthFunction.apply(verts, None, K, float(S), S, True, True, 0.1, 100.0)
+    v, _, fidx, bary = dep.grad_fn.saved_tensors
+    gdep = torch.randn(2, S, S, device="cuda")
+
+    def raster(gv, ws, flag):
+        lib.check(L.g2s_raster_depth_bwd_ex(p(v), None, p(gdep), p(fidx), p(bary), 2, S * S, 2 * (S - 1) ** 2, S,
+                                            (lib.C.c_float * 9)(*K), float(S), 2, p(gv), p(ws),
+                                            0 if ws is None else ws.numel(), flag, st()))
+        return gv.clone()
+    plain = raster(torch.full_like(v, 7.0), None, 0)
+    assert float((raster(torch.zeros_like(v), None, 1) - plain).abs().max()) <= 1e-5 * float(plain.abs().max())
 
     prev = lib.set_deterministic(True)      # one workgroup per image: the sums have a fixed order
     try:
-        plain = call(torch.full((B, 4), 7.0, device="cuda"), False)              # cleared by the library
-        assert torch.equal(call(torch.zeros(B, 4, device="cuda"), True), plain)  # cleared by the caller
-        dirty = call(torch.ones(B, 4, device="cuda"), True)                      # NOT cleared by anyone
+        ws_bytes = L.g2s_raster_bwd_workspace_bytes(2, S * S)
+        plain = raster(torch.empty_like(v), torch.full((ws_bytes,), 7, dtype=torch.uint8, device="cuda"), 0)
+        ws = torch.zeros(ws_bytes, dtype=torch.uint8, device="cuda")
+        assert torch.equal(raster(torch.empty_like(v), ws, 1), plain)
+        plain = shading(torch.full((B, 4), 7.0, device="cuda"), 0)               # cleared by the library
+        assert torch.equal(shading(torch.zeros(B, 4, device="cuda"), 1), plain)  # cleared by the caller
+        dirty = shading(torch.ones(B, 4, device="cuda"), 1)                      # NOT cleared by anyone
         assert float((dirty - plain - 1.0).abs().max()) <= 1e-5 * max(1.0, float(plain.abs().max()))
-        assert L.g2s_set_precleared(0) == 0                                      # restored after every call
+        assert torch.equal(shading(torch.ones(B, 4, device="cuda"), 0), plain)   # nothing carries over to the next call
         # wrapper level: gradients with and without an active pool
         def grads():
             n, l, a = normal.clone().requires_grad_(True), light.clone().requires_grad_(True), albedo.clone().requires_grad_(True)

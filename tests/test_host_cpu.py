@@ -100,6 +100,20 @@ def test_abi_exports_every_declared_symbol():
     assert L.g2s_raster_workspace_bytes(0, 1, 1, 1) == 0
 
 
+def test_abi_argument_counts_match_the_header():
+    """Every declaration of include/g2s.h takes as many parameters as lib.SIGNATURES gives ctypes (which
+    would pass a short or long argument list without complaint)."""
+    header = open(os.path.join(ROOT, "include", "g2s.h")).read()
+    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    header = re.sub(r"//[^\n]*", "", header)
+    decls = re.findall(r"\b(g2s_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", header)
+    assert {name for name, _ in decls} == set(lib.SIGNATURES)
+    for name, params in decls:
+        params = params.strip()
+        n = 0 if params in ("", "void") else len(params.split(","))
+        assert n == len(lib.SIGNATURES[name][1]), (name, n, len(lib.SIGNATURES[name][1]))
+
+
 def test_argument_validation_without_gpu():
     """Validation happens before any launch, so it can be exercised on the CPU box."""
     L = lib.load()
