@@ -23,8 +23,9 @@ __global__ __launch_bounds__(WG_THREADS) void conv_wgrad_kernel(WgradParams p) {
 
 using namespace g2s;
 
-static int wgrad_impl(const float *A, const float *G, float *dw, int B, int Ca, int Cg, int PH, int PW, int GH,
-                      int GW, int k, int stride, int pad, int dw_is_zero, int groups, g2s_stream_t stream) {
+extern "C" int g2s_conv2d_wgrad(const float *A, const float *G, float *dw, int B, int Ca, int Cg, int PH, int PW,
+                                int GH, int GW, int k, int stride, int pad, int dw_is_zero, int groups,
+                                g2s_stream_t stream) {
     WgradParams p;
     int tiles, split;
     const int rc = wgrad_plan(A, G, dw, B, Ca, Cg, PH, PW, GH, GW, k, stride, pad, groups, p, tiles, split);
@@ -35,16 +36,4 @@ static int wgrad_impl(const float *A, const float *G, float *dw, int B, int Ca, 
         return fail(G2S_ERR_LAUNCH, "hipMemsetAsync(dw) failed");
     conv_wgrad_kernel<<<dim3(tiles, split, groups), WG_THREADS, 0, st>>>(p);
     return check_launch("g2s_conv2d_wgrad");
-}
-
-extern "C" int g2s_conv2d_wgrad(const float *A, const float *G, float *dw, int B, int Ca, int Cg,
-                                int PH, int PW, int GH, int GW, int k, int stride, int pad,
-                                int dw_is_zero, g2s_stream_t stream) {
-    return wgrad_impl(A, G, dw, B, Ca, Cg, PH, PW, GH, GW, k, stride, pad, dw_is_zero, 1, stream);
-}
-
-extern "C" int g2s_conv2d_wgrad_grouped(const float *A, const float *G, float *dw, int B, int Ca, int Cg,
-                                        int PH, int PW, int GH, int GW, int k, int stride, int pad,
-                                        int dw_is_zero, int groups, g2s_stream_t stream) {
-    return wgrad_impl(A, G, dw, B, Ca, Cg, PH, PW, GH, GW, k, stride, pad, dw_is_zero, groups, stream);
 }

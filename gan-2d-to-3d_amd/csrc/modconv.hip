@@ -1067,13 +1067,12 @@ struct WgradRider {
 };
 
 // The epilogue of one launch: y = gain * act(sum + noise_w[0] * noise[oy, ox] + bias[m]), act 1 = leaky-ReLU(alpha),
-// 0 = none (gain unused).  NULL pointers drop their term; only g2s_modconv_nba passes a noise (with a bias, act 1).
+// 0 = none (gain unused).  NULL pointers drop their term; only g2s_modconv passes a noise (with a bias, act 1).
 struct Epilogue {
     const float *bias, *noise, *noise_w;
     int act;
     float alpha, gain;
 };
-static const Epilogue kNoEpilogue{nullptr, nullptr, nullptr, 0, 0.0f, 1.0f};
 
 static int conv_launch(const float *x, const float *w, const float *in_scale, const float *out_scale,
                        const Epilogue &ep, float *y, int B, int Cr, int M, int H, int W, const ConvGeom &g,
@@ -1322,26 +1321,18 @@ static int modconv_launch(const float *x, const float *w, const float *in_scale,
                        tile, splitk, stream, y_is_zero, f16_operands, 1, nullptr, plan_needs_zero);
 }
 
-// g2s_modconv + g2s_conv_bias_act in one entry point, with the caller's promise that y is already
-// zero (a slice of a pool cleared once per training step: the split-K / polyphase-hole paths then
-// issue no clear of their own — one graph node less per such launch).
-extern "C" int g2s_modconv_ex(const float *x, const float *w, const float *in_scale, const float *out_scale,
-                              const float *bias, float *y, int B, int Cin, int Cout, int H, int W, int k, int mode,
-                              int transpose, int act, float alpha, float gain, int y_is_zero, g2s_stream_t stream) {
+// The direct kernel with its whole epilogue (a noise is the StyledConv tail, stylegan2-pytorch/model.py:349-355: it
+// comes with a bias and the leaky ReLU) and the caller's promise y_is_zero that y is already zero (a slice of a pool
+// cleared once per training step: the split-K / polyphase-hole paths then issue no clear of their own — one graph
+// node less per such launch).
+extern "C" int g2s_modconv(const float *x, const float *w, const float *in_scale, const float *out_scale,
+                           const float *bias, const float *noise, const float *noise_w, float *y, int B, int Cin,
+                           int Cout, int H, int W, int k, int mode, int transpose, int act, float alpha, float gain,
+                           int y_is_zero, g2s_stream_t stream) {
     G2S_REQUIRE(act == 0 || act == 1, "act must be 0 (none) or 1 (leaky-ReLU)");
-    return modconv_launch(x, w, in_scale, out_scale, Epilogue{bias, nullptr, nullptr, act, alpha, gain}, y, B, Cin,
+    G2S_REQUIRE(!noise || (bias && noise_w && act == 1), "a noise needs bias, noise_w and act = 1");
+    return modconv_launch(x, w, in_scale, out_scale, Epilogue{bias, noise, noise_w, act, alpha, gain}, y, B, Cin,
                           Cout, H, W, k, mode, transpose, stream, false, y_is_zero != 0);
-}
-
-// g2s_modconv_ex with the whole StyledConv tail (stylegan2-pytorch/model.py:349-355) in the epilogue:
-// y = gain * leaky_relu(out_scale * conv(in_scale * x) + noise_w[0] * noise[h, w] + bias[c], alpha).
-extern "C" int g2s_modconv_nba(const float *x, const float *w, const float *in_scale, const float *out_scale,
-                               const float *bias, const float *noise, const float *noise_w, float *y, int B, int Cin,
-                               int Cout, int H, int W, int k, int mode, int transpose, float alpha, float gain,
-                               int y_is_zero, g2s_stream_t stream) {
-    G2S_REQUIRE(bias && noise && noise_w, "bias, noise and noise_w must not be NULL");
-    return modconv_launch(x, w, in_scale, out_scale, Epilogue{bias, noise, noise_w, 1, alpha, gain}, y, B, Cin, Cout,
-                          H, W, k, mode, transpose, stream, false, y_is_zero != 0);
 }
 
 // 1 if that launch adds into a cleared output (split-K slices / polyphase holes), else 0; < 0: error.
@@ -1364,20 +1355,6 @@ extern "C" int g2s_modconv_f16(const float *x, const float *w, const float *in_s
                           Cout, H, W, k, mode, transpose, stream, true);
 }
 
-extern "C" int g2s_modconv(const float *x, const float *w, const float *in_scale,
-                           const float *out_scale, float *y, int B, int Cin, int Cout, int H, int W,
-                           int k, int mode, int transpose, g2s_stream_t stream) {
-    return modconv_launch(x, w, in_scale, out_scale, kNoEpilogue, y, B, Cin, Cout, H, W, k, mode, transpose, stream);
-}
-
-extern "C" int g2s_conv_bias_act(const float *x, const float *w, const float *bias, float *y, int B,
-                                 int Cin, int Cout, int H, int W, int k, int mode, int act,
-                                 float alpha, float gain, g2s_stream_t stream) {
-    G2S_REQUIRE(act == 0 || act == 1, "act must be 0 (none) or 1 (leaky-ReLU)");
-    return modconv_launch(x, w, nullptr, nullptr, Epilogue{bias, nullptr, nullptr, act, alpha, gain}, y, B, Cin, Cout,
-                          H, W, k, mode, 0, stream);
-}
-
 static int conv2d_impl(const float *x, const float *w, const float *bias, float *y, int B, int Cr, int M, int H,
                        int W, int k, int stride, int pad, int adjoint, int w_m_major, int out_h, int out_w,
                        int act, float alpha, float gain, int y_is_zero, int groups, g2s_stream_t stream,
@@ -1398,18 +1375,9 @@ static int conv2d_impl(const float *x, const float *w, const float *bias, float 
                        g, tile, splitk, stream, y_is_zero != 0, false, groups, rider);
 }
 
-extern "C" int g2s_conv2d(const float *x, const float *w, const float *bias, float *y, int B, int Cr,
-                          int M, int H, int W, int k, int stride, int pad, int adjoint, int w_m_major,
-                          int out_h, int out_w, int act, float alpha, float gain, int y_is_zero,
-                          g2s_stream_t stream) {
-    return conv2d_impl(x, w, bias, y, B, Cr, M, H, W, k, stride, pad, adjoint, w_m_major, out_h, out_w, act, alpha,
-                       gain, y_is_zero, 1, stream);
-}
-
-extern "C" int g2s_conv2d_grouped(const float *x, const float *w, const float *bias, float *y, int B, int Cr,
-                                  int M, int H, int W, int k, int stride, int pad, int adjoint, int w_m_major,
-                                  int out_h, int out_w, int act, float alpha, float gain, int y_is_zero,
-                                  int groups, g2s_stream_t stream) {
+extern "C" int g2s_conv2d(const float *x, const float *w, const float *bias, float *y, int B, int Cr, int M, int H,
+                          int W, int k, int stride, int pad, int adjoint, int w_m_major, int out_h, int out_w, int act,
+                          float alpha, float gain, int y_is_zero, int groups, g2s_stream_t stream) {
     return conv2d_impl(x, w, bias, y, B, Cr, M, H, W, k, stride, pad, adjoint, w_m_major, out_h, out_w, act, alpha,
                        gain, y_is_zero, groups, stream);
 }

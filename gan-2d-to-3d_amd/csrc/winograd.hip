@@ -521,10 +521,12 @@ extern "C" int g2s_wino_weights(const float *w, float *U, int Cout, int Cin, int
     return check_launch("g2s_wino_weights");
 }
 
-static int wino_launch(const float *x, const float *U, const float *in_scale, const float *out_scale,
-                       const float *bias, const float *noise, const float *noise_w, float *y, int B, int Cr, int M,
-                       int H, int W, int act, float alpha, float gain, int splitk, float *ws, int64_t ws_floats,
-                       g2s_stream_t stream) {
+extern "C" int g2s_conv3x3_wino(const float *x, const float *U, const float *in_scale, const float *out_scale,
+                                const float *bias, const float *noise, const float *noise_w, float *y, int B, int Cr,
+                                int M, int H, int W, int act, float alpha, float gain, int splitk, float *ws,
+                                int64_t ws_floats, g2s_stream_t stream) {
+    // a noise is the StyledConv tail (stylegan2-pytorch/model.py:349-355): it comes with a bias and the leaky ReLU
+    G2S_REQUIRE(!noise || (bias && noise_w && act == 1), "a noise needs bias, noise_w and act = 1");
     G2S_REQUIRE(x && U && y, "x, U, y must not be NULL");
     G2S_REQUIRE(B > 0 && Cr > 0 && M > 0 && H >= 2 && W >= 2, "sizes must be positive (H, W >= 2)");
     G2S_REQUIRE(act == 0 || act == 1, "act must be 0 (none) or 1 (leaky-ReLU)");
@@ -657,23 +659,4 @@ static int wino_launch(const float *x, const float *U, const float *in_scale, co
         return g2s_noise_bias_act(y, noise, noise_w, bias, y, B, M, H * W, alpha, gain, stream);
     return g2s_fused_bias_act(y, bias, nullptr, y, (int64_t)B * M * H * W, (int64_t)H * W, M, act ? 3 : 1, 0,
                               alpha, act ? gain : 1.0f, G2S_F32, stream);
-}
-
-extern "C" int g2s_conv3x3_wino(const float *x, const float *U, const float *in_scale, const float *out_scale,
-                                const float *bias, float *y, int B, int Cr, int M, int H, int W, int act,
-                                float alpha, float gain, int splitk, float *ws, int64_t ws_floats,
-                                g2s_stream_t stream) {
-    return wino_launch(x, U, in_scale, out_scale, bias, nullptr, nullptr, y, B, Cr, M, H, W, act, alpha, gain, splitk,
-                       ws, ws_floats, stream);
-}
-
-// The same with the whole StyledConv tail (stylegan2-pytorch/model.py:349-355) in the epilogue:
-// y = gain * leaky_relu(out_scale * conv(in_scale * x) + noise_w[0] * noise[h, w] + bias[m], alpha).
-extern "C" int g2s_conv3x3_wino_nba(const float *x, const float *U, const float *in_scale, const float *out_scale,
-                                    const float *bias, const float *noise, const float *noise_w, float *y, int B, int Cr,
-                                    int M, int H, int W, float alpha, float gain, int splitk, float *ws,
-                                    int64_t ws_floats, g2s_stream_t stream) {
-    G2S_REQUIRE(bias && noise && noise_w, "bias, noise and noise_w must not be NULL");
-    return wino_launch(x, U, in_scale, out_scale, bias, noise, noise_w, y, B, Cr, M, H, W, 1, alpha, gain, splitk, ws,
-                       ws_floats, stream);
 }

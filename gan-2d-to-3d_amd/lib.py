@@ -42,12 +42,8 @@ SIGNATURES = {
     "g2s_add_bias_scale": (_i, [_p, _p, _p, _p, _i64, _i64, _i, _f, _p]),
     "g2s_noise_bias_act": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _f, _f, _p]),
     "g2s_upfirdn2d": (_i, [_p, _p, _p] + [_i] * 14 + [_p]),
-    "g2s_modconv": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "g2s_conv_bias_act": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _p]),
-    "g2s_modconv_ex": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _p]),
+    "g2s_modconv": (_i, [_p] * 8 + [_i] * 9 + [_f, _f, _i, _p]),
     "g2s_modconv_needs_zero": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
-    "g2s_modconv_nba": (_i, [_p] * 8 + [_i] * 8 + [_f, _f, _i, _p]),
-    "g2s_conv3x3_wino_nba": (_i, [_p] * 8 + [_i] * 5 + [_f, _f, _i, _p, _i64, _p]),
     "g2s_upfirdn2d_nba": (_i, [_p, _p, _p] + [_i] * 12 + [_p, _p, _p, _f, _f, _p]),
     "g2s_synth_bwd_rows": (_i, [_p] * 13 + [_i, _i, _i, _f, _f, _p]),
     "g2s_channel_sum": (_i, [_p, _p, _i, _i, _i, _p]),
@@ -63,11 +59,9 @@ SIGNATURES = {
     "g2s_wino4_supported": (_i, [_i] * 5),
     "g2s_conv3x3_wino4": (_i, [_p] * 8 + [_i] * 6 + [_f, _f, _i, _p, _i64, _p]),
     "g2s_wino_weights": (_i, [_p, _p, _i, _i, _i, _p]),
-    "g2s_conv3x3_wino": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _f, _i, _p, _i64, _p]),
-    "g2s_conv2d": (_i, [_p, _p, _p, _p] + [_i] * 12 + [_i, _f, _f, _i, _p]),
-    "g2s_conv2d_wgrad": (_i, [_p, _p, _p] + [_i] * 10 + [_i, _p]),
-    "g2s_conv2d_grouped": (_i, [_p, _p, _p, _p] + [_i] * 12 + [_i, _f, _f, _i, _i, _p]),
-    "g2s_conv2d_wgrad_grouped": (_i, [_p, _p, _p] + [_i] * 10 + [_i, _i, _p]),
+    "g2s_conv3x3_wino": (_i, [_p] * 8 + [_i] * 6 + [_f, _f, _i, _p, _i64, _p]),
+    "g2s_conv2d": (_i, [_p, _p, _p, _p] + [_i] * 12 + [_i, _f, _f, _i, _i, _p]),
+    "g2s_conv2d_wgrad": (_i, [_p, _p, _p] + [_i] * 10 + [_i, _i, _p]),
     "g2s_conv2d_bwd": (_i, [_p, _p, _p] + [_i] * 13 + [_p, _p, _p] + [_i] * 8 + [_p]),
     "g2s_adam_chunk": (_i64, []),
     "g2s_adam_step": (_i, [_p, _p, _p, _i, _i, _f, _f, _f, _f, _f, _p]),

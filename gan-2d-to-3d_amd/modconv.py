@@ -53,12 +53,14 @@ class profiled:
         return False
 
 
-def out_size(h, k, mode):
+def _out_hw(H, W, k, mode, transpose):
+    """Output size: PLAIN keeps H x W, UP2 scatters (out (H-1)*2+k), DOWN2 gathers with stride 2 (out (H-k)//2+1);
+    the adjoint geometry (transpose = 1) of UP2 gathers and that of DOWN2 scatters."""
     if mode == PLAIN:
-        return h
-    if mode == UP2:
-        return (h - 1) * 2 + k
-    return (h - k) // 2 + 1
+        return H, W
+    if (mode == UP2) != bool(transpose):
+        return (H - 1) * 2 + k, (W - 1) * 2 + k
+    return (H - k) // 2 + 1, (W - k) // 2 + 1
 
 
 # Operand precision of the FROZEN networks' GEMMs (generator, discriminator, VGG):
@@ -68,25 +70,12 @@ def out_size(h, k, mode):
 OPERANDS = "f32"
 
 
-def _f16_launch(x, w, si, so, bias, mode, transpose, act, alpha, gain, y):
-    B, _, H, W = x.shape
-    Cout, Cin, k, _ = w.shape
-    L = _lib.load()
-    sp = y.shape[2] * y.shape[3] if mode == PLAIN else min(H * W, y.shape[2] * y.shape[3])
-    with profiled(2.0 * B * Cout * Cin * k * k * sp, 4.0 * (x.numel() + w.numel() + y.numel())):
-        _lib.check(L.g2s_modconv_f16(_lib.ptr(x), _lib.ptr(w), _lib.ptr(si), _lib.ptr(so), _lib.ptr(bias),
-                                     _lib.ptr(y), B, Cin, Cout, H, W, k, mode, int(transpose), int(act),
-                                     float(alpha), float(gain), _lib.stream()))
-    return y
-
-
 # Winograd F(2x2, 3x3) for the stride-1 3x3 layers (csrc/winograd.hip).  WINOGRAD = False forces the
 # direct implicit GEMM everywhere; layers with fewer than WINO_MIN_TILES 2x2 output tiles (too few
 # workgroups for the 64-channel x 64-tile blocks) stay on the direct kernel.
 WINOGRAD = True
 WINO_MIN_TILES = 512
 WINO_FORCE = None   # tests / tuning tools: "direct", or a splitk value (0 = library choice) for every 3x3 stride-1 call
-_WINO_U = {}  # (data_ptr, version, shape, transpose) -> (w, U): transformed weights of constant tensors
 
 try:  # measured choices for the workload's own call signatures (tools/tune_wino.py)
     from .wino_tuned import TABLE as _WINO_TABLE
@@ -124,119 +113,115 @@ def wino_choice(x, w, mode, transpose, fused):
     return 0   # F(4x4) only where the table measured it ahead: on unmeasured signatures it lost as often as it won
 
 
-def wino_eligible(x, w, mode, H, W):
-    return wino_choice(x, w, mode, 0, 0) is not None
-
-
-def wino_weights(w, transpose):
-    """U = G g G^T of a constant weight tensor [Cout, Cin, 3, 3] in the library's tiled layout,
-    computed once per (tensor, version, direction)."""
-    key = (w.data_ptr(), w._version, tuple(w.shape), int(transpose))
-    hit = _WINO_U.get(key)
-    if hit is None:
-        if len(_WINO_U) > 256:
-            _WINO_U.clear()
-        Cout, Cin = w.shape[:2]
-        L = _lib.load()
-        M, Cr = (Cin, Cout) if transpose else (Cout, Cin)
-        U = torch.empty(L.g2s_wino_weights_floats(M, Cr), dtype=torch.float32, device=w.device)
-        _lib.check(L.g2s_wino_weights(_lib.ptr(w), _lib.ptr(U), Cout, Cin, int(transpose), _lib.stream()))
-        hit = _WINO_U[key] = (w, U)   # holds `w`: its data_ptr stays unique while cached
-    return hit[1]
-
-
 # Winograd F(4x4, 3x3) (csrc/winograd4.hip) for the large maps: 1.78x fewer MFMA operations than F(2x2).  A choice
 # "w4:k" (WINO_FORCE / the tuned table: wino_choice) sends the launch there with splitk = k (0: library choice);
 # unmeasured signatures stay on F(2x2) (car128_joint, whose batch sizes are not in the table, ran 8 % slower with
 # a fill-based default).  WINO4 = False keeps every Winograd layer on F(2x2).
 WINO4 = os.environ.get("G2S_WINO4", "1") != "0"   # G2S_WINO4=0: measurement runs without the F(4x4) kernel
-_WINO4_U = {}
 
 
 def wino4_supported(B, Cr, M, H, W):
     return WINO4 and _lib.load().g2s_wino4_supported(B, Cr, M, H, W) == 1
 
 
-def wino4_weights(w, transpose):
-    """U = G g G^T (6x6 per channel pair) of a constant weight tensor in the F(4x4) kernel's tiled layout."""
+# transformed weights of constant tensors, one cache per Winograd kernel:
+# kernel -> {(data_ptr, version, shape, transpose): (w, U)}
+_WINO_U = {"winograd": {}, "winograd4": {}}
+
+
+def _wino_weights(w, transpose, kernel):
+    """U = G g G^T of a constant weight tensor [Cout, Cin, 3, 3] in the tiled layout of `kernel` ("winograd":
+    F(2x2), 4x4 per channel pair; "winograd4": F(4x4), 6x6), computed once per (tensor, version, direction)."""
+    cache = _WINO_U[kernel]
     key = (w.data_ptr(), w._version, tuple(w.shape), int(transpose))
-    hit = _WINO4_U.get(key)
+    hit = cache.get(key)
     if hit is None:
-        if len(_WINO4_U) > 256:
-            _WINO4_U.clear()
+        if len(cache) > 256:
+            cache.clear()
         Cout, Cin = w.shape[:2]
         L = _lib.load()
         M, Cr = (Cin, Cout) if transpose else (Cout, Cin)
-        U = torch.empty(L.g2s_wino4_weights_floats(M, Cr), dtype=torch.float32, device=w.device)
-        _lib.check(L.g2s_wino4_weights(_lib.ptr(w), _lib.ptr(U), Cout, Cin, int(transpose), _lib.stream()))
-        hit = _WINO4_U[key] = (w, U)
+        floats, transform = ((L.g2s_wino4_weights_floats, L.g2s_wino4_weights) if kernel == "winograd4"
+                             else (L.g2s_wino_weights_floats, L.g2s_wino_weights))
+        U = torch.empty(floats(M, Cr), dtype=torch.float32, device=w.device)
+        _lib.check(transform(_lib.ptr(w), _lib.ptr(U), Cout, Cin, int(transpose), _lib.stream()))
+        hit = cache[key] = (w, U)   # holds `w`: its data_ptr stays unique while cached
     return hit[1]
 
 
-def _wino_launch(x, w, in_scale, out_scale, bias, transpose, act, alpha, gain, y, splitk=0, noise=None, noise_w=None):
-    """One stride-1 3x3 launch on a Winograd kernel: `splitk` is wino_choice's answer — "w4:k" = F(4x4), an int =
-    F(2x2) with that partition.  noise / noise_w: the StyledConv tail (then bias and act = 1 are required)."""
+def _conv(x, w, in_scale, out_scale, mode, transpose, out_shape, route, bias=None, noise=None, noise_w=None, act=0,
+          alpha=0.0, gain=1.0):
+    """The one launch site of the convolution kernels of the frozen networks:
+        y [out_shape] = gain * act(out_scale * conv(in_scale * x, w) + noise_w * noise + bias, alpha)
+    act 1: leaky-ReLU, 0: none (gain unused); None drops a term; a noise comes with a bias and act 1.
+    route: "f16" — fp16 operands (g2s_modconv_f16); wino_choice's answer — an int: F(2x2) with that splitk, "w4:k":
+    F(4x4) with splitk k; None — the direct implicit GEMM, whose outputs of launches that add partial sums (split-K
+    slices, polyphase holes) come from the step's cleared pool when one is active."""
     B, Cr, H, W = x.shape
-    M = y.shape[1]
+    Cout, Cin, k, _ = w.shape
+    M = out_shape[1]
+    act, alpha, gain = int(act), float(alpha), float(gain)
     L = _lib.load()
-    flop, nbytes = 2.0 * B * M * Cr * 9 * H * W, 4.0 * (x.numel() + w.numel() + y.numel())
-    if isinstance(splitk, str):   # "w4:k"
-        U = wino4_weights(w, transpose)
+    p = _lib.ptr
+    y = None
+    if route is None and L.g2s_modconv_needs_zero(B, Cin, Cout, H, W, k, mode, int(transpose),
+                                                  int(in_scale is not None or out_scale is not None),
+                                                  int(bias is not None or act != 0)) == 1:
+        y = _zp.take(out_shape, x.device)
+    zeroed = y is not None
+    if y is None:
+        y = torch.empty(out_shape, dtype=torch.float32, device=x.device)
+    # algorithmic FLOP: 2 * B * Cout * Cin * k^2 * (spatial positions of the un-strided side);
+    # algorithmic bytes: each operand once
+    oh, ow = out_shape[2], out_shape[3]
+    flop = 2.0 * B * Cout * Cin * k * k * (oh * ow if mode == PLAIN else min(H * W, oh * ow))
+    nbytes = 4.0 * (x.numel() + w.numel() + y.numel())
+    if route is None:
+        with profiled(flop, nbytes):
+            _lib.check(L.g2s_modconv(p(x), p(w), p(in_scale), p(out_scale), p(bias), p(noise), p(noise_w), p(y), B,
+                                     Cin, Cout, H, W, k, mode, int(transpose), act, alpha, gain, int(zeroed),
+                                     _lib.stream()))
+    elif route == "f16":
+        with profiled(flop, nbytes):
+            _lib.check(L.g2s_modconv_f16(p(x), p(w), p(in_scale), p(out_scale), p(bias), p(y), B, Cin, Cout, H, W, k,
+                                         mode, int(transpose), act, alpha, gain, _lib.stream()))
+    elif isinstance(route, str):   # "w4:k"
+        U = _wino_weights(w, transpose, "winograd4")
         with profiled(flop, nbytes, 2.0 * 36 * B * (H // 4) * (W // 4) * M * Cr, "winograd4"):
-            _lib.check(L.g2s_conv3x3_wino4(_lib.ptr(x), _lib.ptr(U), _lib.ptr(in_scale), _lib.ptr(out_scale),
-                                           _lib.ptr(bias), _lib.ptr(noise), _lib.ptr(noise_w), _lib.ptr(y), B, Cr, M, H, W,
-                                           int(act), float(alpha), float(gain), int(splitk[3:] or 0), *_lib.split_ws(),
+            _lib.check(L.g2s_conv3x3_wino4(p(x), p(U), p(in_scale), p(out_scale), p(bias), p(noise), p(noise_w), p(y),
+                                           B, Cr, M, H, W, act, alpha, gain, int(route[3:] or 0), *_lib.split_ws(),
                                            _lib.stream()))
-        return y
-    U = wino_weights(w, transpose)
-    tiles = B * ((H + 1) // 2) * ((W + 1) // 2)
-    with profiled(flop, nbytes, 2.0 * 16 * tiles * M * Cr):
-        if noise is not None:
-            _lib.check(L.g2s_conv3x3_wino_nba(_lib.ptr(x), _lib.ptr(U), _lib.ptr(in_scale), _lib.ptr(out_scale),
-                                              _lib.ptr(bias), _lib.ptr(noise), _lib.ptr(noise_w), _lib.ptr(y), B, Cr, M,
-                                              H, W, float(alpha), float(gain), int(splitk), *_lib.split_ws(),
-                                              _lib.stream()))
-        else:
-            _lib.check(L.g2s_conv3x3_wino(_lib.ptr(x), _lib.ptr(U), _lib.ptr(in_scale), _lib.ptr(out_scale),
-                                          _lib.ptr(bias), _lib.ptr(y), B, Cr, M, H, W, int(act), float(alpha),
-                                          float(gain), int(splitk), *_lib.split_ws(), _lib.stream()))
+    else:
+        U = _wino_weights(w, transpose, "winograd")
+        tiles = B * ((H + 1) // 2) * ((W + 1) // 2)
+        with profiled(flop, nbytes, 2.0 * 16 * tiles * M * Cr):
+            _lib.check(L.g2s_conv3x3_wino(p(x), p(U), p(in_scale), p(out_scale), p(bias), p(noise), p(noise_w), p(y),
+                                          B, Cr, M, H, W, act, alpha, gain, int(route), *_lib.split_ws(),
+                                          _lib.stream()))
     return y
 
 
 def modconv_nba_raw(x, w, in_scale, out_scale, bias, noise, noise_w, slope, gain):
-    """StyledConv (plain 3x3 or 1x1) with its whole tail in the convolution's epilogue (g2s_modconv_nba /
-    g2s_conv3x3_wino_nba): gain * leaky_relu(out_scale * conv(in_scale * x) + noise_w * noise + bias, slope).
-    fp32 kernels only."""
+    """StyledConv (plain 3x3 or 1x1) with its whole tail in the convolution's epilogue (a noise to g2s_modconv /
+    g2s_conv3x3_wino / g2s_conv3x3_wino4): gain * leaky_relu(out_scale * conv(in_scale * x) + noise_w * noise + bias,
+    slope).  fp32 kernels only."""
     _lib.require_cuda(x, w, in_scale, out_scale, bias, noise, noise_w)
     if OPERANDS != "f32" or x.dtype != torch.float32:
         raise RuntimeError("modconv_nba: fp32 kernels only")
     x, w = x.contiguous(), w.contiguous()
     B, C, H, W = x.shape
-    Cout, Cin, k, _ = w.shape
+    Cout, Cin = w.shape[:2]
     if C != Cin or tuple(noise.shape[-2:]) != (H, W) or noise.numel() != H * W:
         raise RuntimeError("modconv_nba: shape mismatch")
     si, so = in_scale.contiguous(), out_scale.contiguous()
     bias, noise, noise_w = bias.contiguous(), noise.contiguous(), noise_w.contiguous()
-    L = _lib.load()
-    choice = wino_choice(x, w, PLAIN, 0, 1)
-    if choice is not None:
-        y = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device)
-        return _wino_launch(x, w, si, so, bias, 0, 1, slope, gain, y, choice, noise, noise_w)
-    y = None
-    if L.g2s_modconv_needs_zero(B, Cin, Cout, H, W, k, PLAIN, 0, 1, 1) == 1:
-        y = _zp.take((B, Cout, H, W), x.device)
-    zeroed = y is not None
-    if y is None:
-        y = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device)
-    with profiled(2.0 * B * Cout * Cin * k * k * H * W, 4.0 * (x.numel() + w.numel() + y.numel())):
-        _lib.check(L.g2s_modconv_nba(_lib.ptr(x), _lib.ptr(w), _lib.ptr(si), _lib.ptr(so), _lib.ptr(bias), _lib.ptr(noise),
-                                     _lib.ptr(noise_w), _lib.ptr(y), B, Cin, Cout, H, W, k, PLAIN, 0, float(slope),
-                                     float(gain), int(zeroed), _lib.stream()))
-    return y
+    return _conv(x, w, si, so, PLAIN, 0, (B, Cout, H, W), wino_choice(x, w, PLAIN, 0, 1), bias, noise, noise_w, 1,
+                 slope, gain)
 
 
 def modconv_raw(x, w, in_scale, out_scale, mode, transpose):
-    """Direct call of g2s_modconv.  w is always [Cout, Cin, k, k]."""
+    """The modulated convolution without epilogue (Winograd / direct / fp16-operand kernel).  w is always
+    [Cout, Cin, k, k]."""
     _lib.require_cuda(x, w, in_scale, out_scale)
     if x.dtype != torch.float32 or w.dtype != torch.float32:
         raise RuntimeError("modconv: float32 only")
@@ -246,52 +231,15 @@ def modconv_raw(x, w, in_scale, out_scale, mode, transpose):
     Cout, Cin, k, _ = w.shape
     if C != (Cout if transpose else Cin):
         raise RuntimeError(f"modconv: x has {C} channels, expected {Cout if transpose else Cin}")
-    if transpose:
-        # adjoint geometry: UP2^T gathers with stride 2, DOWN2^T scatters
-        oh = {PLAIN: H, UP2: (H - k) // 2 + 1, DOWN2: (H - 1) * 2 + k}[mode]
-        ow = {PLAIN: W, UP2: (W - k) // 2 + 1, DOWN2: (W - 1) * 2 + k}[mode]
-        cy = Cin
-    else:
-        oh, ow = out_size(H, k, mode), out_size(W, k, mode)
-        cy = Cout
+    oh, ow = _out_hw(H, W, k, mode, transpose)
+    cy = Cin if transpose else Cout
     for name, t, c in (("in_scale", in_scale, C), ("out_scale", out_scale, cy)):
         if t is not None and (t.shape != (B, c) or t.dtype != torch.float32):
             raise RuntimeError(f"modconv: {name} must be float32 [{B}, {c}]")
     si = None if in_scale is None else in_scale.contiguous()
     so = None if out_scale is None else out_scale.contiguous()
-    f16 = OPERANDS == "f16" and not w.requires_grad
-    choice = None if f16 else wino_choice(x, w, mode, transpose, 0)
-    if f16 or choice is not None:
-        y = torch.empty((B, cy, oh, ow), dtype=torch.float32, device=x.device)
-        if f16:
-            return _f16_launch(x, w, si, so, None, mode, transpose, 0, 0.0, 1.0, y)
-        return _wino_launch(x, w, si, so, None, transpose, 0, 0.0, 1.0, y, choice)
-    return _direct_launch(x, w, si, so, None, mode, transpose, 0, 0.0, 1.0, (B, cy, oh, ow))
-
-
-def _direct_launch(x, w, si, so, bias, mode, transpose, act, alpha, gain, out_shape):
-    """The direct implicit-GEMM kernel (g2s_modconv_ex).  Outputs of launches that add partial sums
-    (split-K slices, polyphase holes) come from the step's cleared pool when one is active."""
-    B, _, H, W = x.shape
-    Cout, Cin, k, _ = w.shape
-    L = _lib.load()
-    fused = bias is not None or act != 0
-    y = None
-    if L.g2s_modconv_needs_zero(B, Cin, Cout, H, W, k, mode, int(transpose), int(si is not None or so is not None),
-                                int(fused)) == 1:
-        y = _zp.take(out_shape, x.device)
-    zeroed = y is not None
-    if y is None:
-        y = torch.empty(out_shape, dtype=torch.float32, device=x.device)
-    # algorithmic FLOP: 2 * B * Cout * Cin * k^2 * (spatial positions of the un-strided side);
-    # algorithmic bytes: each operand once
-    oh, ow = out_shape[2], out_shape[3]
-    sp = min(H * W, oh * ow) if mode != PLAIN else oh * ow
-    with profiled(2.0 * B * Cout * Cin * k * k * sp, 4.0 * (x.numel() + w.numel() + y.numel())):
-        _lib.check(L.g2s_modconv_ex(_lib.ptr(x), _lib.ptr(w), _lib.ptr(si), _lib.ptr(so), _lib.ptr(bias), _lib.ptr(y),
-                                    B, Cin, Cout, H, W, k, mode, int(transpose), int(act), float(alpha), float(gain),
-                                    int(zeroed), _lib.stream()))
-    return y
+    route = "f16" if OPERANDS == "f16" and not w.requires_grad else wino_choice(x, w, mode, transpose, 0)
+    return _conv(x, w, si, so, mode, transpose, (B, cy, oh, ow), route)
 
 
 def rows_dot_scale(a, b, s=None, inv=None, want_out=True, want_dot=True):
@@ -492,16 +440,9 @@ def conv_bias_act_raw(x, w, bias, mode=PLAIN, alpha=0.0, gain=1.0):
     x, w, bias = x.contiguous(), w.contiguous(), bias.contiguous()
     B, Cin, H, W = x.shape
     Cout, _, k, _ = w.shape
-    oh, ow = out_size(H, k, mode), out_size(W, k, mode)
-    choice = None if OPERANDS == "f16" else wino_choice(x, w, mode, 0, 1)
-    if OPERANDS == "f16" or choice is not None:
-        y = torch.empty((B, Cout, oh, ow), dtype=torch.float32, device=x.device)
-        if OPERANDS == "f16":
-            _f16_launch(x, w, None, None, bias, mode, 0, 1, alpha, gain, y)
-        else:
-            _wino_launch(x, w, None, None, bias, 0, 1, alpha, gain, y, choice)
-        return y
-    return _direct_launch(x, w, None, None, bias, mode, 0, 1, alpha, gain, (B, Cout, oh, ow))
+    oh, ow = _out_hw(H, W, k, mode, 0)
+    route = "f16" if OPERANDS == "f16" else wino_choice(x, w, mode, 0, 1)
+    return _conv(x, w, None, None, mode, 0, (B, Cout, oh, ow), route, bias, act=1, alpha=alpha, gain=gain)
 
 
 def relu_gate(g, y, alpha=0.0, gain=1.0):
@@ -514,7 +455,7 @@ class ConvBiasActFunction(Function):
     """gain * leaky_relu(conv(x, w) + bias, alpha) for a FROZEN network (no weight / bias gradient):
     the VGG16 trunk of LPIPS (conv3x3 + bias + ReLU, lpips/pretrained_networks.py:97-135) and the
     discriminator's ConvLayer (EqualConv2d + FusedLeakyReLU, stylegan2-pytorch/model.py:630-676).
-    Forward is one launch (g2s_conv_bias_act); backward = activation slope from the saved output
+    Forward is one launch (conv_bias_act_raw); backward = activation slope from the saved output
     (g2s_fused_bias_act, act 3 / grad 1) + the data-gradient GEMM."""
 
     @staticmethod

@@ -105,7 +105,7 @@ class _SplitHalves(torch.autograd.Function):
 def run_fused_pair(mods_a, mods_b, x, train_a=True, train_b=True):
     """Two structurally identical module lists on the SAME input as one pass: activations carry the
     channels of net a followed by those of net b, convolutions run as grouped launches
-    (g2s_conv2d_grouped, groups = 2; the first layer is one plain convolution with both nets' filters),
+    (g2s_conv2d with groups = 2; the first layer is one plain convolution with both nets' filters),
     GroupNorm sees twice the groups.  From the first layer whose parameters differ in shape (the nets'
     heads: GAN2Shape/networks.py:53-76,144-167) the two halves continue on their own.  Per net the
     arithmetic is that of run_fused.  train_x = False: that net's parameters get no gradient (the

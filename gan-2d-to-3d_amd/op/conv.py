@@ -63,20 +63,24 @@ class PassArena:
         return v
 
 
+def _out_size(H, W, k, stride, pad, adjoint):
+    """Output size of a convolution (adjoint = 0) or of its adjoint, the transposed convolution without output
+    padding (adjoint = 1)."""
+    if adjoint:
+        return (H - 1) * stride - 2 * pad + k, (W - 1) * stride - 2 * pad + k
+    return (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+
+
 def conv_out_hw(mod, H, W):
-    k, s, p = mod.kernel_size[0], mod.stride[0], mod.padding[0]
-    if isinstance(mod, torch.nn.ConvTranspose2d):
-        return (H - 1) * s - 2 * p + k, (W - 1) * s - 2 * p + k
-    return (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    return _out_size(H, W, mod.kernel_size[0], mod.stride[0], mod.padding[0],
+                     isinstance(mod, torch.nn.ConvTranspose2d))
 
 
 def _conv2d_raw(x, w, bias, Cr, M, k, stride, pad, adjoint, m_major, out_hw, act, slope, out=None, groups=1):
-    """Cr -> M channels PER GROUP; x has groups * Cr channels, y groups * M (g2s_conv2d_grouped)."""
+    """Cr -> M channels PER GROUP; x has groups * Cr channels, y groups * M (g2s_conv2d).  out_hw: the output size of
+    an adjoint launch (None: the smallest, _out_size); ignored otherwise."""
     B, _, H, W = x.shape
-    if adjoint:
-        oh, ow = out_hw if out_hw else ((H - 1) * stride - 2 * pad + k, (W - 1) * stride - 2 * pad + k)
-    else:
-        oh, ow = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    oh, ow = out_hw if adjoint and out_hw else _out_size(H, W, k, stride, pad, adjoint)
     zeroed = out is not None
     y = out if zeroed else torch.empty((B, groups * M, oh, ow), dtype=torch.float32, device=x.device)
     assert tuple(y.shape) == (B, groups * M, oh, ow) and x.shape[1] == groups * Cr
@@ -84,16 +88,9 @@ def _conv2d_raw(x, w, bias, Cr, M, k, stride, pad, adjoint, m_major, out_hw, act
     from gan2shape_amd.modconv import profiled
     sp = H * W if adjoint else oh * ow  # every (input pixel, tap) pair of the strided side once
     with profiled(2.0 * B * groups * Cr * M * k * k * sp, 4.0 * (x.numel() + w.numel() + y.numel())):
-        if groups == 1:
-            _lib.check(L.g2s_conv2d(_lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(y), B, Cr, M, H, W, k,
-                                    stride, pad, int(adjoint), int(m_major), oh if adjoint else 0,
-                                    ow if adjoint else 0, 1 if act else 0, float(slope), 1.0, int(zeroed),
-                                    _lib.stream()))
-        else:
-            _lib.check(L.g2s_conv2d_grouped(_lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(y), B, Cr, M, H, W,
-                                            k, stride, pad, int(adjoint), int(m_major), oh if adjoint else 0,
-                                            ow if adjoint else 0, 1 if act else 0, float(slope), 1.0,
-                                            int(zeroed), groups, _lib.stream()))
+        _lib.check(L.g2s_conv2d(_lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(y), B, Cr, M, H, W, k, stride, pad,
+                                int(adjoint), int(m_major), oh if adjoint else 0, ow if adjoint else 0,
+                                1 if act else 0, float(slope), 1.0, int(zeroed), groups, _lib.stream()))
     return y
 
 
@@ -105,12 +102,8 @@ def _wgrad(A, G, k, stride, pad, out=None, groups=1):
     zeroed = out is not None
     dw = out if zeroed else torch.empty((groups * Ca, Cg, k, k), dtype=torch.float32, device=A.device)
     L = _lib.load()
-    if groups == 1:
-        _lib.check(L.g2s_conv2d_wgrad(_lib.ptr(A), _lib.ptr(G), _lib.ptr(dw), B, Ca, Cg, PH, PW, GH, GW, k,
-                                      stride, pad, int(zeroed), _lib.stream()))
-    else:
-        _lib.check(L.g2s_conv2d_wgrad_grouped(_lib.ptr(A), _lib.ptr(G), _lib.ptr(dw), B, Ca, Cg, PH, PW, GH, GW,
-                                              k, stride, pad, int(zeroed), groups, _lib.stream()))
+    _lib.check(L.g2s_conv2d_wgrad(_lib.ptr(A), _lib.ptr(G), _lib.ptr(dw), B, Ca, Cg, PH, PW, GH, GW, k, stride, pad,
+                                  int(zeroed), groups, _lib.stream()))
     return dw
 
 
@@ -159,11 +152,7 @@ class ConvFunction(Function):
         b = None if bias is None else bias.contiguous()
         out = None
         if arena is not None:
-            H, W = x.shape[2], x.shape[3]
-            if transposed:
-                oh, ow = (H - 1) * stride - 2 * pad + k, (W - 1) * stride - 2 * pad + k
-            else:
-                oh, ow = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+            oh, ow = _out_size(x.shape[2], x.shape[3], k, stride, pad, transposed)
             out = arena.take_fwd((x.shape[0], groups * cout, oh, ow))
             if ctx.needs_input_grad[0]:
                 arena.reserve_bwd(x.numel())

@@ -8,8 +8,8 @@ What the reference — and this package's op-by-op path — runs per StyledConv 
 noise`, fused_bias_act, and in backward the gate, the data-gradient GEMM and three reductions, every one
 a full pass over the activation in HBM.  Here:
 
-  forward    plain layers: convolution with noise + bias + leaky-ReLU in its epilogue (g2s_modconv_nba /
-             g2s_conv3x3_wino_nba) — the pre-activation is never stored; up-sampling layers: the
+  forward    plain layers: convolution with noise + bias + leaky-ReLU in its epilogue (modconv_nba_raw: a noise
+             to g2s_modconv / g2s_conv3x3_wino[4]) — the pre-activation is never stored; up-sampling layers: the
              transposed convolution, then the Blur with the same tail in its store (g2s_upfirdn2d_nba);
   backward   per activation x between two layers ONE row pass (g2s_synth_bwd_rows) reads x and the
              data-gradients of its consumers (next convolution, ToRGB) and produces the consumers' style

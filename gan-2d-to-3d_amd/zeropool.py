@@ -3,7 +3,7 @@
 The split-K slices of the direct convolution kernel (small layers: too few tiles for 256 CUs) and
 the polyphase classes that leave holes add into an output that must start at zero.  The library
 clears such an output itself (hipMemsetAsync) — one more graph node per launch, 36 of step 1's 319.
-Here each step kind clears ONE buffer at its start and hands out slices (g2s_modconv_ex,
+Here each step kind clears ONE buffer at its start and hands out slices (g2s_modconv,
 y_is_zero = 1).  The buffer is a fresh tensor of the caching allocator per step (sized by what the
 previous step of that kind asked for), slices are tensors on its storage (they keep it alive; each has its
 own autograd version counter), nothing is ever handed out twice: no lifetime hazards, and inside a captured HIP graph it lives in the graph's

@@ -263,44 +263,33 @@ int g2s_upfirdn2d_nba(const float *x, const float *k, float *y, int major, int c
  *                    here H, W are the sizes of x and must be odd: out (H-k)/2+1)
  * x [B, C_in_of_this_call, H, W] f32; in_scale [B, C_in_of_this_call] or NULL;
  * out_scale [B, C_out_of_this_call] or NULL; y fully overwritten.  k in {1, 3}.
+ *
+ * Epilogue, on the convolution's output c = out_scale[b,o] * conv(in_scale * x)[b,o,h,w]:
+ *   y = c + bias[o]                                                          act = 0
+ *   y = gain * leaky_relu(c + noise_w[0] * noise[h,w] + bias[o], alpha)     act = 1 (alpha = 0, gain = 1: ReLU)
+ * bias [C_out_of_this_call] or NULL.  noise [OH, OW] f32 (one map for all samples and channels) or NULL, noise_w a
+ * DEVICE pointer to 1 float: with a noise, the epilogue is the WHOLE StyledConv tail (stylegan2-pytorch/model.py:
+ * 321-355: ModulatedConv2d, NoiseInjection, FusedLeakyReLU — the reference runs conv, `image + weight * noise` and
+ * fused_bias_act as three ops), and bias, noise_w and act = 1 are required.  The frozen VGG16 of the LPIPS loss
+ * (conv3x3 + bias + ReLU, lpips/pretrained_networks.py:97-135) and the discriminator's ConvLayer take bias + act
+ * without scales.  A split-K launch finishes with g2s_fused_bias_act / g2s_noise_bias_act in place.
+ * y_is_zero != 0: the caller's promise that y is already all zeros — e.g. a slice of a pool cleared ONCE per
+ * training step (gan-2d-to-3d_amd/zeropool.py).  Launches that add partial sums into y (split-K slices of small
+ * layers; polyphase classes that leave holes) then skip their own clear: one graph node less each (36 of step 1's
+ * 319 nodes were such clears).
+ * g2s_modconv_needs_zero answers, without launching anything, whether that signature adds into a cleared output (1)
+ * or overwrites y (0) under the calling thread's current tuning state, so that only those outputs are taken from the
+ * pool.  has_scales = in_scale or out_scale is given; fused = a bias / activation epilogue is present.
  * ---------------------------------------------------------------------------------------- */
 #define G2S_CONV_PLAIN 0
 #define G2S_CONV_UP2 1
 #define G2S_CONV_DOWN2 2
 
-int g2s_modconv(const float *x, const float *w, const float *in_scale, const float *out_scale,
-                float *y, int B, int Cin, int Cout, int H, int W, int k, int mode, int transpose,
-                g2s_stream_t stream);
-
-/* Plain convolution on the same kernel with a fused epilogue:
- *   y = act(conv(x, w) + bias[o]),  act = 0: identity, 1: leaky-ReLU(alpha) * gain (alpha = 0, gain = 1: ReLU).
- * Used for the frozen VGG16 of the LPIPS loss (conv3x3 + bias + ReLU, lpips/pretrained_networks.py:97-135).
- * Same geometry modes as g2s_modconv with transpose = 0; bias may be NULL. */
-int g2s_conv_bias_act(const float *x, const float *w, const float *bias, float *y, int B, int Cin,
-                      int Cout, int H, int W, int k, int mode, int act, float alpha, float gain,
-                      g2s_stream_t stream);
-
-/* g2s_modconv and g2s_conv_bias_act behind one entry point (in_scale / out_scale / bias may each be
- * NULL, act as above), plus y_is_zero: the caller's promise that y is already all zeros — e.g. a slice
- * of a pool cleared ONCE per training step (gan-2d-to-3d_amd/zeropool.py).  Launches that add partial
- * sums into y (split-K slices of small layers; polyphase classes that leave holes) then skip their own
- * clear: one graph node less each (36 of step 1's 319 nodes were such clears).
- * g2s_modconv_needs_zero answers, without launching anything, whether that signature adds into a
- * cleared output (1) or overwrites y (0) under the calling thread's current tuning state, so that
- * only those outputs are taken from the pool.  fused = a bias / activation epilogue is present. */
-int g2s_modconv_ex(const float *x, const float *w, const float *in_scale, const float *out_scale,
-                   const float *bias, float *y, int B, int Cin, int Cout, int H, int W, int k, int mode,
-                   int transpose, int act, float alpha, float gain, int y_is_zero, g2s_stream_t stream);
+int g2s_modconv(const float *x, const float *w, const float *in_scale, const float *out_scale, const float *bias,
+                const float *noise, const float *noise_w, float *y, int B, int Cin, int Cout, int H, int W, int k,
+                int mode, int transpose, int act, float alpha, float gain, int y_is_zero, g2s_stream_t stream);
 int g2s_modconv_needs_zero(int B, int Cin, int Cout, int H, int W, int k, int mode, int transpose,
                            int has_scales, int fused);
-/* g2s_modconv_ex with the WHOLE StyledConv tail in the epilogue (stylegan2-pytorch/model.py:321-355: ModulatedConv2d,
- * NoiseInjection, FusedLeakyReLU — the reference runs conv, `image + weight * noise` and fused_bias_act as three ops):
- *     y = gain * leaky_relu(out_scale[b,o] * conv(in_scale * x)[b,o,h,w] + noise_w[0] * noise[h,w] + bias[o], alpha)
- * noise [OH, OW] f32 (one map for all samples and channels), noise_w a DEVICE pointer to 1 float, bias [Cout].
- * A split-K launch finishes with g2s_noise_bias_act in place. */
-int g2s_modconv_nba(const float *x, const float *w, const float *in_scale, const float *out_scale, const float *bias,
-                    const float *noise, const float *noise_w, float *y, int B, int Cin, int Cout, int H, int W, int k,
-                    int mode, int transpose, float alpha, float gain, int y_is_zero, g2s_stream_t stream);
 
 /* General 2-D convolution on the same fp32-MFMA implicit-GEMM kernel: the trained nets of the step
  * (depth / albedo / viewpoint / lighting / offset-encoder nets, GAN2Shape/networks.py:23-244:
@@ -310,38 +299,31 @@ int g2s_modconv_nba(const float *x, const float *w, const float *in_scale, const
  *   adjoint = 1: y[b,m,iy*s+ky-p,ix*s+kx-p] += x[b,c,iy,ix] W(m,c,ky,kx), out out_h x out_w, 0 = (H-1)s-2p+k
  *                (up to s-1 more, as a strided Conv2d's input can be)    (ConvTranspose2d forward; Conv2d dgrad)
  *   W(m,c,ky,kx) = w[(m*Cr + c)*k*k + ky*k + kx] if w_m_major (w is [M,Cr,k,k]) else w[(c*M + m)*k*k + ...]
- * x [B,Cr,H,W], y [B,M,...] f32, fully overwritten; bias [M] or NULL, act as g2s_conv_bias_act.
+ * x [B,Cr,H,W], y [B,M,...] f32, fully overwritten; bias [M] or NULL; act 0: none, 1: leaky-ReLU(alpha) * gain.
  * k 1..5, stride 1 or 2, 0 <= pad < k.
  * g2s_conv2d_wgrad: dw[a,g,ky,kx] = sum_{b,py,px} A[b,a,py,px] * G[b,g,py*s+ky-p,px*s+kx-p]
  *   (zero outside G), A [B,Ca,PH,PW], G [B,Cg,GH,GW], dw [Ca,Cg,k,k] fully overwritten.
  *   Conv2d weight gradient: A = grad_out, G = input; ConvTranspose2d: A = input, G = grad_out.
  *   Summation over pixels is split over workgroups and added with float atomics.
  * y_is_zero / dw_is_zero != 0: the caller hands over zero-filled outputs (e.g. slices of one cleared
- *   arena per network pass), so the split-K paths skip their own clear of the output. */
+ *   arena per network pass), so the split-K paths skip their own clear of the output.
+ * groups (1..8): that many independent convolutions in one launch — two structurally identical trained nets
+ *   (depth + albedo, viewpoint + lighting: GAN2Shape/networks.py:53-167 differ only in their last layer) run with
+ *   their channels side by side: x [B, groups*Cr, H, W], y [B, groups*M, ...], w and bias hold the groups back to
+ *   back ([groups][M][Cr][k][k], or [groups][Cr][M][k][k] when w_m_major = 0); for the weight gradient
+ *   A [B, groups*Ca, ...], G [B, groups*Cg, ...], dw [groups][Ca][Cg][k][k].  Per group the arithmetic is that of
+ *   groups = 1, the shapes above. */
 int g2s_conv2d(const float *x, const float *w, const float *bias, float *y, int B, int Cr, int M, int H,
                int W, int k, int stride, int pad, int adjoint, int w_m_major, int out_h, int out_w,
-               int act, float alpha, float gain, int y_is_zero, g2s_stream_t stream);
+               int act, float alpha, float gain, int y_is_zero, int groups, g2s_stream_t stream);
 int g2s_conv2d_wgrad(const float *A, const float *G, float *dw, int B, int Ca, int Cg, int PH, int PW,
-                     int GH, int GW, int k, int stride, int pad, int dw_is_zero, g2s_stream_t stream);
-/* `groups` independent convolutions in one launch — two structurally identical trained nets (depth +
- * albedo, viewpoint + lighting: GAN2Shape/networks.py:53-167 differ only in their last layer) run
- * with their channels side by side: x [B, groups*Cr, H, W], y [B, groups*M, ...], w and bias hold the
- * groups back to back ([groups][M][Cr][k][k], or [groups][Cr][M][k][k] when w_m_major = 0); for the
- * weight gradient A [B, groups*Ca, ...], G [B, groups*Cg, ...], dw [groups][Ca][Cg][k][k].  Per
- * group the arithmetic is that of g2s_conv2d / g2s_conv2d_wgrad. */
-int g2s_conv2d_grouped(const float *x, const float *w, const float *bias, float *y, int B, int Cr, int M,
-                       int H, int W, int k, int stride, int pad, int adjoint, int w_m_major, int out_h,
-                       int out_w, int act, float alpha, float gain, int y_is_zero, int groups,
-                       g2s_stream_t stream);
-int g2s_conv2d_wgrad_grouped(const float *A, const float *G, float *dw, int B, int Ca, int Cg, int PH,
-                             int PW, int GH, int GW, int k, int stride, int pad, int dw_is_zero, int groups,
-                             g2s_stream_t stream);
+                     int GH, int GW, int k, int stride, int pad, int dw_is_zero, int groups, g2s_stream_t stream);
 
 /* Backward of one convolution layer of the trained nets as ONE launch: the data-gradient
- *   g2s_conv2d[_grouped](gy, w, NULL, gx, B, Cr, M, H, W, k, stride, pad, adjoint, w_m_major, out_h, out_w,
- *                        0, 0, 1, gx_is_zero, [groups,] stream)
+ *   g2s_conv2d(gy, w, NULL, gx, B, Cr, M, H, W, k, stride, pad, adjoint, w_m_major, out_h, out_w,
+ *              0, 0, 1, gx_is_zero, groups, stream)
  * and the weight-gradient
- *   g2s_conv2d_wgrad[_grouped](A, G, dw, B, Ca, Cg, PH, PW, GH, GW, k, stride, pad, dw_is_zero, [groups,] stream)
+ *   g2s_conv2d_wgrad(A, G, dw, B, Ca, Cg, PH, PW, GH, GW, k, stride, pad, dw_is_zero, groups, stream)
  * of the same layer (k, stride, pad, B, groups shared) in one grid — the two are independent and
  * latency-bound at these sizes, so the layer costs the longer of the two.  Results are those of
  * the two separate calls.  (torch's ConvolutionBackward of nn.Conv2d / nn.ConvTranspose2d,
@@ -377,8 +359,8 @@ int g2s_adam_step(const g2s_adam_tensor *tensors, const int *chunk0, const float
                   int n_chunks, float lr, float beta1, float beta2, float eps, float weight_decay,
                   g2s_stream_t stream);
 
-/* fp16-OPERAND form of g2s_modconv / g2s_conv_bias_act (BASELINE config 5, "fp16 MFMA path"): same
- * arguments and geometry; x, w, y stay fp32 in memory, both GEMM operands are rounded to fp16 on
+/* fp16-OPERAND form of g2s_modconv (BASELINE config 5, "fp16 MFMA path"): the same geometry and arguments without
+ * noise / noise_w / y_is_zero; x, w, y stay fp32 in memory, both GEMM operands are rounded to fp16 on
  * their way into LDS and multiplied by v_mfma_f32_32x32x8_f16 with fp32 accumulation.  bias (NULL ok)
  * and act (0 none / 1 leaky-ReLU(alpha) * gain) form the epilogue.  1x1 and 3x3 kernels only.
  * Results differ from the fp32 kernels at the 1e-3 level (fp16 rounding of the operands). */
@@ -397,9 +379,11 @@ int g2s_modconv_f16(const float *x, const float *w, const float *in_scale, const
  *   written to U (g2s_wino_weights_floats(M, Cr) floats, tiled layout private to the library).
  *   transpose = 0: M = Cout, Cr = Cin (forward).  transpose = 1: M = Cin, Cr = Cout, taps flipped
  *   (the data-gradient of the forward map).  Done once per weight tensor by the caller.
- * g2s_conv3x3_wino: y[b,m] = act(out_scale[b,m] * sum_c conv3x3(in_scale[b,c] * x[b,c], w(m,c)) + bias[m])
- *   x [B, Cr, H, W], y [B, M, H, W]; in_scale [B, Cr], out_scale [B, M], bias [M] may be NULL;
- *   act 0: none, 1: leaky-ReLU(alpha) * gain.  splitk = 0: partition chosen by the library — whole
+ * g2s_conv3x3_wino: y[b,m] = act(out_scale[b,m] * sum_c conv3x3(in_scale[b,c] * x[b,c], w(m,c)) + noise_w[0] *
+ *   noise[h,w] + bias[m]); x [B, Cr, H, W], y [B, M, H, W]; in_scale [B, Cr], out_scale [B, M], bias [M], noise
+ *   [H, W] may be NULL; act 0: none, 1: leaky-ReLU(alpha) * gain.  A noise is the StyledConv tail (see g2s_modconv):
+ *   it requires bias, noise_w and act = 1, and the reduce passes below add it with the bias.
+ *   splitk = 0: partition chosen by the library — whole
  *   tiles, or "stream-K": equal runs of (tile, K tile) units over 256 workgroups when whole tiles
  *   would fill the last round of CUs badly; splitk > 0: that K split of every tile; splitk < 0:
  *   stream-K over -splitk workgroups.  Partial sums meet by float atomics in a cleared y and the
@@ -413,14 +397,9 @@ int g2s_modconv_f16(const float *x, const float *w, const float *in_scale, const
 size_t g2s_wino_weights_floats(int M, int Cr);
 int g2s_wino_weights(const float *w, float *U, int Cout, int Cin, int transpose, g2s_stream_t stream);
 int g2s_conv3x3_wino(const float *x, const float *U, const float *in_scale, const float *out_scale,
-                     const float *bias, float *y, int B, int Cr, int M, int H, int W, int act,
-                     float alpha, float gain, int splitk, float *ws, int64_t ws_floats, g2s_stream_t stream);
-/* The same with the StyledConv tail in the epilogue (see g2s_modconv_nba): act = leaky-ReLU, bias / noise / noise_w
- * required; the split-K and stream-K reduce passes add the noise term with the bias. */
-int g2s_conv3x3_wino_nba(const float *x, const float *U, const float *in_scale, const float *out_scale,
-                         const float *bias, const float *noise, const float *noise_w, float *y, int B, int Cr, int M,
-                         int H, int W, float alpha, float gain, int splitk, float *ws, int64_t ws_floats,
-                         g2s_stream_t stream);
+                     const float *bias, const float *noise, const float *noise_w, float *y, int B, int Cr, int M,
+                     int H, int W, int act, float alpha, float gain, int splitk, float *ws, int64_t ws_floats,
+                     g2s_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * The same map as Winograd F(4x4, 3x3) (csrc/winograd4.hip): 36 multiplications per 16 outputs — 1.78x fewer than
@@ -452,7 +431,7 @@ int g2s_mfma_lds_probe(float *out, int blocks, int waves, int iters, int acc_agp
 
 /* Tuning hook (tools/tune_modconv.py): force the tile configuration (0: 128x128, 1: 128x64,
  * 2: 64x64, 3: 32x128, 4: 64x128 output channels x pixels) and/or the split-K factor of the calling thread's following
- * g2s_modconv / g2s_conv_bias_act / g2s_conv2d launches (slices of the deepest polyphase class of a
+ * g2s_modconv / g2s_conv2d launches (slices of the deepest polyphase class of a
  * strided scatter; shallower classes get proportionally fewer); -1 restores the built-in choice
  * (measured tables csrc/modconv_tuned.inc / conv2d_tuned.inc, else a heuristic), tile = -2 selects
  * the heuristic alone.  Results do not depend on the choice beyond the fp32 summation order. */

@@ -421,7 +421,7 @@ def _nba_expected(pre, bias, noise, nw, alpha, gain):
     (3, 70, 130, 22),      # ragged channels, tiles spanning batch entries
 ])
 def test_styledconv_tail_in_the_epilogue_vs_oracle(L, B, cin, cout, H):
-    """g2s_modconv_nba / g2s_conv3x3_wino_nba (modconv.modconv_nba_raw): the modulated 3x3 convolution with
+    """g2s_modconv / g2s_conv3x3_wino with a noise (modconv.modconv_nba_raw): the modulated 3x3 convolution with
     NoiseInjection + FusedLeakyReLU in its epilogue (stylegan2-pytorch/model.py:321-355) against the C oracle's
     convolution followed by the tail in numpy — every tile x split-K of the direct kernel, every partition of the
     Winograd kernel (whole tiles, split-K with the reduce pass, stream-K with its reduce pass, atomics without a
@@ -463,9 +463,10 @@ def test_styledconv_tail_in_the_epilogue_vs_oracle(L, B, cin, cout, H):
         mc.WINOGRAD, mc.WINO_FORCE = saved
 
 
-def test_styledconv_tail_without_scales_keeps_the_noise(L):
-    """g2s_modconv_nba with NULL scales on a shape the thin 1x1 kernel takes (fromRGB-like: 3 -> 32 channels over
-    >= 64 K pixels): that kernel has no noise term, so the call must stay on the MFMA kernel, whose epilogue adds it."""
+def test_noise_without_scales_stays_on_the_mfma_kernel(L):
+    """g2s_modconv with a noise and NULL scales on a shape the thin 1x1 kernel takes (fromRGB-like: 3 -> 32 channels
+    over >= 64 K pixels): that kernel has no noise term, so the call must stay on the MFMA kernel, whose epilogue adds
+    it."""
     from gan2shape_amd import lib
     B, cin, cout, H = 8, 3, 32, 128
     rng = np.random.default_rng(11)
@@ -478,8 +479,8 @@ def test_styledconv_tail_without_scales_keeps_the_noise(L):
     xd, wd, bd, nd, nwd = dev(x), dev(w), dev(bias), dev(noise), dev(np.array([nw], np.float32))
     y = torch.empty(B, cout, H, H, device="cuda")
     L.g2s_modconv_tune(-1, -1)
-    lib.check(L.g2s_modconv_nba(lib.ptr(xd), lib.ptr(wd), None, None, lib.ptr(bd), lib.ptr(nd), lib.ptr(nwd),
-                                lib.ptr(y), B, cin, cout, H, H, 1, PLAIN, 0, alpha, gain, 0, lib.stream()))
+    lib.check(L.g2s_modconv(lib.ptr(xd), lib.ptr(wd), None, None, lib.ptr(bd), lib.ptr(nd), lib.ptr(nwd),
+                            lib.ptr(y), B, cin, cout, H, H, 1, PLAIN, 0, 1, alpha, gain, 0, lib.stream()))
     _check(y, exp, cin, "StyledConv tail, NULL scales, thin-eligible shape")
 
 

@@ -432,7 +432,7 @@ def test_conv_function_matches_torch_f64(g2s, B, cin, cout, H, k, stride, pad, t
 ])
 def test_fused_backward_launch_equals_the_two_launches(g2s, B, groups, cin, cout, H, k, stride, pad, transposed):
     """g2s_conv2d_bwd (data-gradient + weight-gradient of one layer in one grid) against
-    g2s_conv2d[_grouped] + g2s_conv2d_wgrad[_grouped], with the data-gradient on its 64x64 tile (one
+    g2s_conv2d + g2s_conv2d_wgrad, with the data-gradient on its 64x64 tile (one
     grid) and forced onto the 128-wide tiles (the entry point then launches the two kernels itself)."""
     from gan2shape_amd import lib
     from gan2shape_amd.op.conv import _conv2d_raw, _conv_bwd_raw, _wgrad
@@ -562,7 +562,7 @@ def test_renderer_texture_helpers_on_gpu(g2s):
 @pytest.mark.parametrize("names,B", [(("DepthNet", "AlbedoNet"), 1), (("ViewpointNet", "LightingNet"), 1),
                                      (("ViewpointNet", "LightingNet"), 5)])
 def test_paired_nets_equal_the_two_nets(g2s, names, B):
-    """forward_pair (one pass with twice the channels: g2s_conv2d_grouped / g2s_conv2d_wgrad_grouped,
+    """forward_pair (one pass with twice the channels: g2s_conv2d / g2s_conv2d_wgrad with groups = 2,
     GroupNorm over twice the groups) against the same two nets run one after the other: outputs
     and every parameter gradient — also with one net frozen (step 1: only the albedo net trains)."""
     import copy

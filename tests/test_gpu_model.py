@@ -343,7 +343,7 @@ def _smooth_ref(pred):
 
 
 def test_vgg_trunk_on_mfma_kernel_matches_miopen():
-    """conv3x3 + bias + ReLU through g2s_conv_bias_act vs torch.nn (MIOpen), features and the
+    """conv3x3 + bias + ReLU through modconv.conv_bias_act_raw vs torch.nn (MIOpen), features and the
     gradient w.r.t. the input image."""
     import gan2shape_amd  # noqa: F401
     from gan2shape_amd.lpips import VGG16Features

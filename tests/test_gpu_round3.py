@@ -1,5 +1,5 @@
 """-m gpu: round-3 additions of the C ABI — reproducible launch partitions (g2s_set_deterministic),
-the step-wide cleared pool (g2s_modconv_ex / g2s_modconv_needs_zero, zeropool.py) — against the
+the step-wide cleared pool (g2s_modconv's y_is_zero / g2s_modconv_needs_zero, zeropool.py) — against the
 oracle and against the default launch mode."""
 import math
 

@@ -114,15 +114,23 @@ def test_abi_argument_counts_match_the_header():
         assert n == len(lib.SIGNATURES[name][1]), (name, n, len(lib.SIGNATURES[name][1]))
 
 
-def test_argument_validation_without_gpu():
+def test_argument_validation_before_any_launch():
     """Validation happens before any launch, so it can be exercised on the CPU box."""
     L = lib.load()
     rc = L.g2s_fused_bias_act(None, None, None, None, 16, 1, 1, 3, 0, 0.2, 1.0, 0, None)
     assert rc == -1 and b"NULL" in L.g2s_last_error()
     rc = L.g2s_upfirdn2d(None, None, None, 1, 4, 4, 4, 4, 1, 1, 1, 1, 0, 0, 0, 0, 0, None)
     assert rc == -1
-    rc = L.g2s_modconv(None, None, None, None, None, 1, 1, 1, 4, 4, 3, 0, 0, None)
+    rc = L.g2s_modconv(None, None, None, None, None, None, None, None, 1, 1, 1, 4, 4, 3, 0, 0, 0, 0.0, 1.0, 0, None)
     assert rc == -1
+    # a noise is the StyledConv tail: without a bias, or with act = 0, both convolution kernels refuse it first
+    # (the host buffer stands in for device memory and B = 0 would be refused next: nothing is launched)
+    d = (lib.C.c_float * 4)()
+    for bias, act in ((None, 1), (d, 0)):
+        rc = L.g2s_modconv(d, d, None, None, bias, d, d, d, 0, 4, 4, 4, 4, 3, 0, 0, act, 0.2, 1.0, 0, None)
+        assert rc == -1 and b"noise" in L.g2s_last_error(), (bias, act)
+        rc = L.g2s_conv3x3_wino(d, d, None, None, bias, d, d, d, 0, 4, 4, 4, 4, act, 0.2, 1.0, 0, None, 0, None)
+        assert rc == -1 and b"noise" in L.g2s_last_error(), (bias, act)
     K = (lib.C.c_float * 9)(1, 0, 0, 0, 1, 0, 0, 0, 1)
     rc = L.g2s_raster_depth_fwd(None, None, 1, 16, 18, 4, K, 4.0, 2, 1, 0.1, 100.0, None, None, None,
                                 None, 0, None)

@@ -1,4 +1,4 @@
-"""Per-launch census of the MFMA convolution kernel (g2s_modconv / g2s_conv_bias_act) in one eager
+"""Per-launch census of the MFMA convolution kernels (g2s_modconv / g2s_conv3x3_wino) in one eager
 iteration of each step kind: shape, time (HIP events), TFLOP/s.  python tools/conv_census.py [kind...]"""
 import collections
 import os
@@ -40,16 +40,11 @@ def wrap(name, shape_of):
     setattr(L, name, g)
 
 
-# g2s_modconv(x,w,in_scale,out_scale,y,B,Cin,Cout,H,W,k,mode,transpose,stream)
-wrap("g2s_modconv", lambda a: (a[5], a[6], a[7], a[8], a[9], a[10], a[11], a[12], a[2] is not None, a[3] is not None))
-# g2s_conv_bias_act(x,w,bias,y,B,Cin,Cout,H,W,k,mode,act,alpha,gain,stream)
-wrap("g2s_conv_bias_act", lambda a: (a[4], a[5], a[6], a[7], a[8], a[9], a[10], 0, False, False))
+# g2s_modconv(x,w,in_scale,out_scale,bias,noise,noise_w,y,B,Cin,Cout,H,W,k,mode,transpose,act,alpha,gain,y_is_zero,stream)
+wrap("g2s_modconv", lambda a: (a[8], a[9], a[10], a[11], a[12], a[13], a[14], a[15], a[2] is not None, a[3] is not None))
 
-# g2s_modconv_ex(x,w,in_scale,out_scale,bias,y,B,Cin,Cout,H,W,k,mode,transpose,act,alpha,gain,y_is_zero,stream)
-wrap("g2s_modconv_ex", lambda a: (a[6], a[7], a[8], a[9], a[10], a[11], a[12], a[13], a[2] is not None, a[3] is not None))
-
-# g2s_conv3x3_wino(x,U,in_scale,out_scale,bias,y,B,Cr,M,H,W,act,alpha,gain,splitk,ws,ws_floats,stream)
-wrap("g2s_conv3x3_wino", lambda a: (a[6], a[7], a[8], a[9], a[10], 3, 0, 0, a[2] is not None, a[3] is not None))
+# g2s_conv3x3_wino(x,U,in_scale,out_scale,bias,noise,noise_w,y,B,Cr,M,H,W,act,alpha,gain,splitk,ws,ws_floats,stream)
+wrap("g2s_conv3x3_wino", lambda a: (a[8], a[9], a[10], a[11], a[12], 3, 0, 0, a[2] is not None, a[3] is not None))
 
 for kind in [int(x) for x in sys.argv[1:]] or [1, 2, 3]:
     r.run(kind)
