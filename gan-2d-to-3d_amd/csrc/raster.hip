@@ -31,12 +31,12 @@
 // association order of the 2x2 average.
 #include "g2s_common.h"
 #include "raster_core.h"
+#include "raster_scatter.h"
 #include <limits.h>
 #include <stdlib.h>
 
 namespace g2s {
 
-constexpr int TILE = 8;      // samples per tile side (64 samples = one wavefront)
 constexpr int CAP = 64;      // LDS face-list capacity per wavefront
 constexpr int QCAP = 128;    // fragment queue ring (drained at 64, refilled by at most 64)
 constexpr int WAVES = 4;     // wavefronts per workgroup, all working on one tile
@@ -462,22 +462,6 @@ struct BwdParams {
     long long *gfix;  // deterministic mode: the same sums as 2^-40 fixed point (integer adds commute)
 };
 
-// Deterministic mode accumulates in 64-bit fixed point (LDS and global integer atomics): the sums no
-// longer depend on the order the waves arrive in.  Resolution 2^-40 ~ 9e-13, range +-8.4e6 per
-// component; a non-finite contribution is not representable and is dropped.
-constexpr float FIX_SCALE = 1099511627776.0f;  // 2^40
-__device__ __forceinline__ long long to_fix(float v) { return __float2ll_rn(v * FIX_SCALE); }
-__device__ __forceinline__ float from_fix(long long v) { return (float)((double)v * (1.0 / 1099511627776.0)); }
-__device__ __forceinline__ void acc_add(float *dst, float v) { unsafeAtomicAdd(dst, v); }
-__device__ __forceinline__ void acc_add(long long *dst, float v) {
-    atomicAdd(reinterpret_cast<unsigned long long *>(dst), (unsigned long long)to_fix(v));
-}
-__device__ __forceinline__ void acc_add(long long *dst, long long v) {
-    atomicAdd(reinterpret_cast<unsigned long long *>(dst), (unsigned long long)v);
-}
-__device__ __forceinline__ void lds_add(float *dst, float v) { atomicAdd(dst, v); }
-__device__ __forceinline__ void lds_add(long long *dst, float v) { acc_add(dst, v); }
-
 // One wave per 8x8-sample tile (4 tiles per workgroup).  The 2x2 super-samples of a pixel mostly hit
 // the same face: before the atomics, x- and then y-neighbours with the same winning face merge
 // their nine partial gradients through shuffles, so a face's vertices receive one atomic triple per
@@ -530,88 +514,23 @@ __global__ __launch_bounds__(256) void raster_bwd_samples(BwdParams p) {
             acc[3 * k + 2] = gz[k];
         }
     }
-#pragma unroll
-    for (int step = 0; step < 2; step++) {
-        const int m = step ? 8 : 1;
-        const int pfn = __shfl_xor(fn, m);
-        const bool same = fn >= 0 && pfn == fn;
-#pragma unroll
-        for (int k = 0; k < 9; k++) {
-            const float o = __shfl_xor(acc[k], m);
-            if (same) acc[k] += o;
-        }
-        if (same && (lane & m)) fn = -1;  // the upper lane of a merged pair retires
-    }
-    // per-wave LDS hash table keyed by vertex id: neighbouring faces of a tile share vertices, so
-    // the tile's contributions are summed with LDS atomics and each distinct vertex reaches global
-    // memory once (three float atomics) instead of once per merged sample group and corner
-    constexpr int HS = 128;
-    __shared__ int hkey[4][HS];
-    __shared__ ACC hval[4][HS][3];
-    for (int i2 = lane; i2 < HS; i2 += 64) {
-        hkey[wave][i2] = -1;
-        hval[wave][i2][0] = hval[wave][i2][1] = hval[wave][i2][2] = (ACC)0;
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (fn >= 0) {
-        for (int k = 0; k < 3; k++) {
-            int slot = (v[k] * 0x9E3779B1u) >> 25;  // top 7 bits: 0 .. HS-1
-            bool done = false;
-            for (int probe = 0; probe < 16 && !done; probe++) {
-                const int old = atomicCAS(&hkey[wave][slot], -1, v[k]);
-                if (old == -1 || old == v[k]) {
-                    lds_add(&hval[wave][slot][0], acc[3 * k]);
-                    lds_add(&hval[wave][slot][1], acc[3 * k + 1]);
-                    lds_add(&hval[wave][slot][2], acc[3 * k + 2]);
-                    done = true;
-                }
-                slot = (slot + 1) & (HS - 1);
-            }
-            if (!done) {  // crowded table (many distinct vertices in one tile): straight to memory
-                ACC *dst = gout + ((size_t)b * p.N + v[k]) * 3;
-                acc_add(dst + 0, acc[3 * k]);
-                acc_add(dst + 1, acc[3 * k + 1]);
-                acc_add(dst + 2, acc[3 * k + 2]);
-            }
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    for (int i2 = lane; i2 < HS; i2 += 64) {
-        const int key = hkey[wave][i2];
-        if (key >= 0) {
-            ACC *dst = gout + ((size_t)b * p.N + key) * 3;
-            acc_add(dst + 0, hval[wave][i2][0]);
-            acc_add(dst + 1, hval[wave][i2][1]);
-            acc_add(dst + 2, hval[wave][i2][2]);
-        }
-    }
+    merge_same_face(acc, fn, lane);
+    // the tile's vertex partials meet in a per-wave LDS table (raster_scatter.h)
+    __shared__ VertexTable<ACC> table[4];
+    ACC *const gout_b = gout + (size_t)b * p.N * 3;
+    vt_clear(table[wave], lane);
+    if (fn >= 0)
+        for (int k = 0; k < 3; k++) vt_add(table[wave], v[k], acc[3 * k], acc[3 * k + 1], acc[3 * k + 2], gout_b);
+    vt_flush(table[wave], lane, gout_b);
 }
 
 __global__ __launch_bounds__(256) void raster_bwd_project(BwdParams p) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)p.B * p.N) return;
-    const float *q = p.verts + i * 3;
-    float *g = p.gacc + i * 3;
-    float gx, gy, gz;
-    if (p.gfix) {
-        const long long *f = p.gfix + i * 3;
-        project_backward(q[0], q[1], q[2], p.cam, from_fix(f[0]), from_fix(f[1]), from_fix(f[2]), gx, gy, gz);
-    } else {
-        project_backward(q[0], q[1], q[2], p.cam, g[0], g[1], g[2], gx, gy, gz);
-    }
-    g[0] = gx;
-    g[1] = gy;
-    g[2] = gz;
+    project_backward_vertex(p.verts, p.gacc, p.gfix, p.cam, i);
 }
 
 static int implicit_blocks(int S) { return (S - 1 + 7) / 8; }
-
-static int make_cam(const float *K, float orig_size, Cam &c) {
-    G2S_REQUIRE(K != nullptr, "K must be a host pointer to 9 floats");
-    G2S_REQUIRE(K[6] == 0.0f && K[7] == 0.0f && K[8] == 1.0f, "K third row must be 0 0 1");
-    c = Cam{K[0], K[1], K[2], K[3], K[4], K[5], orig_size};
-    return G2S_OK;
-}
 
 static int check_shape(const int32_t *faces, int B, int N, int F, int S, int ssaa) {
     G2S_REQUIRE(B > 0 && N > 0 && F > 0 && S > 0, "B, n_verts, n_faces, S must be positive");

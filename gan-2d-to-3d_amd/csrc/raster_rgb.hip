@@ -1,7 +1,9 @@
 // raster_rgb.hip — texture path of the rasterizer: nr.Renderer.render_rgb as GAN2Shape's
 // visualisation helpers use it (GAN2Shape/renderer/renderer.py:196,230,248,272,275: render_yaw,
 // render_view, render_given_view(grid_sample=False) with texture cubes from
-// renderer/utils.py:83-109).  Forward only (nothing in the reference differentiates through it).
+// renderer/utils.py:83-109), and its backward: the gradient of the texture lookup w.r.t. the textures
+// (exact: the forward is affine in them) and w.r.t. the vertices with the winner of every sample held
+// fixed (no silhouette term; the external package's edge-sweep heuristic is not rebuilt).
 //
 // Second pass over the maps the depth rasterizer (raster.hip) saves — winning face id and clamped,
 // renormalised barycentric weights per supersample: per sample the texture cube of the winning
@@ -13,6 +15,7 @@
 // (PARITY UNPINNED, like the depth path); the oracle restates them independently on the CPU.
 #include "g2s_common.h"
 #include "raster_core.h"
+#include "raster_scatter.h"
 
 namespace g2s {
 
@@ -105,6 +108,211 @@ __global__ void raster_rgb_kernel(RgbParams p) {
     for (int c = 0; c < p.C; c++) p.out[(((size_t)b * p.C + c) * p.S + r) * p.S + c0] = sum[c] * inv;
 }
 
+// ---------------------------------------------------------------------------------- backward
+struct RgbBwdParams {
+    const float *verts;      // [B, N, 3]
+    const int32_t *faces;    // [F, 3] or NULL (implicit regular grid)
+    const int32_t *face_idx; // [B, is, is]
+    const float *bary;       // [B, is, is, 3]
+    const float *tex;        // [B, F, ts, ts, ts, C]
+    const float *grad_rgb;   // [B, C, S, S]
+    int B, N, F, S, is, ssaa, ts, C;
+    float eps;
+    Cam cam;
+    void *gtex;  // [B, F, ts, ts, ts, C] sums: float, or 2^-40 fixed point in deterministic mode
+    void *gver;  // [B, N, 3] sums of (g_u, g_v, g_z) of the projected vertices, same two forms
+};
+
+// One wave per 8x8-sample tile (4 tiles per workgroup), lane = raster sample, as raster_bwd_samples.
+//   textures  adjoint of the trilinear read: the eight corner weights times the sample's share of
+//             grad_rgb.  MERGE (ts == 2): every sample of a face reads the same eight cells, so the 8 x C
+//             partials of same-face neighbours are merged through shuffles before the atomics;
+//             otherwise each sample adds to its own cells.
+//   vertices  colour -> t_k (derivative of the trilinear read, zero where a clamp is active)
+//             -> a_k = w_k / z_k through t_k = (ts - 1) a_k / sum_j a_j -> (w, z); w are the screen-space
+//             barycentrics, whose motion with the projected vertices is dw_k = -(is / 2) w_l (fi[3k] dx_l +
+//             fi[3k+1] dy_l) (derivative of the inverse vertex matrix of face_inverse); the lookup position
+//             comes from the saved weights, so that forward and backward agree on cell and clamp state.
+//             Nine partials per sample, merged and scattered like the depth backward's.
+template <typename ACC, bool WANT_T, bool WANT_V, bool MERGE>
+__global__ __launch_bounds__(256) void raster_rgb_bwd_samples(RgbBwdParams p) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int tiles_side = (p.is + TILE - 1) / TILE;
+    const int tile = blockIdx.x * 4 + wave, b = blockIdx.y;
+    if (tile >= tiles_side * tiles_side) return;  // whole wave
+    const int xi = (tile % tiles_side) * TILE + (lane & 7), yi = (tile / tiles_side) * TILE + (lane >> 3);
+    const bool inside = xi < p.is && yi < p.is;
+    const size_t si = ((size_t)b * p.is + (inside ? yi : 0)) * p.is + (inside ? xi : 0);
+    int fn = inside ? p.face_idx[si] : -1;
+    const int ts = p.ts;
+    float g[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (fn >= 0) {
+        const int fr = p.is - 1 - yi;
+        const float inv = 1.0f / (float)(p.ssaa * p.ssaa);
+        bool any = false;
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+            if (c < p.C) {
+                g[c] = p.grad_rgb[(((size_t)b * p.C + c) * p.S + fr / p.ssaa) * p.S + xi / p.ssaa] * inv;
+                any = any || g[c] != 0.0f;
+            }
+        if (!any) fn = -1;  // masked pixels contribute exact zeros
+    }
+    int v[3] = {0, 0, 0};
+    int ti[3] = {0, 0, 0};
+    float w[3] = {0, 0, 0}, z[3] = {1, 1, 1}, tf[3] = {0, 0, 0}, a[3] = {0, 0, 0};
+    float depth = 0.0f;
+    bool live[3] = {false, false, false};  // t_k strictly between its clamps
+    bool rev = false;
+    int gidx = 0;
+    if (fn >= 0) {
+        gidx = fn % p.F;
+        rev = fn >= p.F;
+        if (p.faces) {
+            v[0] = p.faces[3 * gidx];
+            v[1] = p.faces[3 * gidx + 1];
+            v[2] = p.faces[3 * gidx + 2];
+        } else {
+            implicit_face(gidx, p.S, v);
+        }
+        if (rev) {
+            const int t = v[0];
+            v[0] = v[2];
+            v[2] = t;
+        }
+        for (int k = 0; k < 3; k++) {
+            w[k] = p.bary[3 * si + k];
+            z[k] = p.verts[((size_t)b * p.N + v[k]) * 3 + 2];
+            a[k] = w[k] / z[k];
+        }
+        depth = 1.0f / (a[0] + a[1] + a[2]);
+        const float hi = (float)(ts - 1) - p.eps;
+        for (int k = 0; k < 3; k++) {
+            const float tu = w[k] * (float)(ts - 1) * (depth / z[k]);
+            live[k] = tu > 0.0f && tu < hi;
+            float t = fmaxf(tu, 0.0f);
+            t = fminf(t, hi);
+            ti[k] = (int)t;
+            tf[k] = t - (float)ti[k];
+        }
+    }
+    // cell of corner pn in the geometric face's cube (the reversed copy reads it with axes 0 and 2 swapped)
+    auto cell = [&](int pn) {
+        int idx[3];
+        for (int k = 0; k < 3; k++) idx[k] = ((pn >> k) & 1) ? min(ti[k] + 1, ts - 1) : ti[k];
+        return rev ? (idx[2] * ts + idx[1]) * ts + idx[0] : (idx[0] * ts + idx[1]) * ts + idx[2];
+    };
+    const size_t cube = ((size_t)b * p.F + gidx) * ts * ts * ts * p.C;
+
+    if (WANT_T) {
+        ACC *const gt = reinterpret_cast<ACC *>(p.gtex);
+        if (MERGE) {
+            float part[32];
+#pragma unroll
+            for (int pn = 0; pn < 8; pn++) {
+                float wt = 1.0f;
+#pragma unroll
+                for (int k = 0; k < 3; k++) wt *= ((pn >> k) & 1) ? tf[k] : 1.0f - tf[k];
+#pragma unroll
+                for (int c = 0; c < 4; c++) part[4 * pn + c] = fn >= 0 ? wt * g[c] : 0.0f;
+            }
+            int ft = fn;
+            merge_same_face(part, ft, lane);
+            if (ft >= 0) {
+#pragma unroll
+                for (int pn = 0; pn < 8; pn++) {
+                    ACC *dst = gt + cube + (size_t)cell(pn) * p.C;
+#pragma unroll
+                    for (int c = 0; c < 4; c++)
+                        if (c < p.C) acc_add(dst + c, part[4 * pn + c]);
+                }
+            }
+        } else if (fn >= 0) {
+            for (int pn = 0; pn < 8; pn++) {
+                float wt = 1.0f;
+                for (int k = 0; k < 3; k++) wt *= ((pn >> k) & 1) ? tf[k] : 1.0f - tf[k];
+                if (wt == 0.0f) continue;
+                ACC *dst = gt + cube + (size_t)cell(pn) * p.C;
+#pragma unroll
+                for (int c = 0; c < 4; c++)
+                    if (c < p.C) acc_add(dst + c, wt * g[c]);
+            }
+        }
+    }
+
+    if (WANT_V) {
+        ACC *const gout_b = reinterpret_cast<ACC *>(p.gver) + (size_t)b * p.N * 3;
+        int fv = fn;
+        float acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (fv >= 0 && !(live[0] || live[1] || live[2])) fv = -1;  // constant under every clamp: exact zeros
+        if (fv >= 0) {
+            // d colour . g / d t_k: the corner sums with the k-th factor replaced by its derivative (-1, +1)
+            float gtk[3] = {0.0f, 0.0f, 0.0f};
+            for (int pn = 0; pn < 8; pn++) {
+                const float *tx = p.tex + cube + (size_t)cell(pn) * p.C;
+                float s = 0.0f;
+#pragma unroll
+                for (int c = 0; c < 4; c++)
+                    if (c < p.C) s += g[c] * tx[c];
+                float f[3];
+                for (int k = 0; k < 3; k++) f[k] = ((pn >> k) & 1) ? tf[k] : 1.0f - tf[k];
+                gtk[0] += (((pn >> 0) & 1) ? s : -s) * (f[1] * f[2]);
+                gtk[1] += (((pn >> 1) & 1) ? s : -s) * (f[0] * f[2]);
+                gtk[2] += (((pn >> 2) & 1) ? s : -s) * (f[0] * f[1]);
+            }
+            for (int k = 0; k < 3; k++)
+                if (!live[k]) gtk[k] = 0.0f;
+            // t_k = (ts - 1) a_k D, D = 1 / sum_j a_j:  g_a[j] = (ts - 1) D (g_t[j] - D sum_k g_t[k] a_k)
+            const float dot = (gtk[0] * a[0] + gtk[1] * a[1] + gtk[2] * a[2]) * depth;
+            float gw[3], gz[3];
+            for (int k = 0; k < 3; k++) {
+                const float ga = (float)(ts - 1) * depth * (gtk[k] - dot);
+                gw[k] = ga / z[k];
+                gz[k] = -ga * a[k] / z[k];
+            }
+            float px[3], py[3], fi[9];
+            for (int k = 0; k < 3; k++) {
+                const float *q = p.verts + ((size_t)b * p.N + v[k]) * 3;
+                project(q[0], q[1], q[2], p.cam, px[k], py[k]);
+            }
+            face_inverse(px[0], py[0], px[1], py[1], px[2], py[2], p.is, fi);
+            const float sx = -(gw[0] * fi[0] + gw[1] * fi[3] + gw[2] * fi[6]) * (float)p.is / 2.0f;
+            const float sy = -(gw[0] * fi[1] + gw[1] * fi[4] + gw[2] * fi[7]) * (float)p.is / 2.0f;
+            for (int k = 0; k < 3; k++) {
+                acc[3 * k] = sx * w[k];
+                acc[3 * k + 1] = sy * w[k];
+                acc[3 * k + 2] = gz[k];
+            }
+        }
+        merge_same_face(acc, fv, lane);
+        __shared__ VertexTable<ACC> table[4];
+        vt_clear(table[wave], lane);
+        if (fv >= 0)
+            for (int k = 0; k < 3; k++) vt_add(table[wave], v[k], acc[3 * k], acc[3 * k + 1], acc[3 * k + 2], gout_b);
+        vt_flush(table[wave], lane, gout_b);
+    }
+}
+
+__global__ __launch_bounds__(256) void raster_rgb_bwd_project(const float *verts, float *gacc, const long long *gfix,
+                                                              Cam cam, long n) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) project_backward_vertex(verts, gacc, gfix, cam, i);
+}
+
+__global__ __launch_bounds__(256) void raster_rgb_bwd_unfix(const long long *fix, float *out, long n) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = from_fix(fix[i]);
+}
+
+template <typename ACC, bool MERGE>
+static void launch_rgb_bwd(const RgbBwdParams &p, bool want_t, bool want_v, hipStream_t st) {
+    const int tiles = cdiv(p.is, TILE) * cdiv(p.is, TILE);
+    const dim3 grid(cdiv(tiles, 4), p.B);
+    if (want_t && want_v) raster_rgb_bwd_samples<ACC, true, true, MERGE><<<grid, 256, 0, st>>>(p);
+    else if (want_t) raster_rgb_bwd_samples<ACC, true, false, MERGE><<<grid, 256, 0, st>>>(p);
+    else raster_rgb_bwd_samples<ACC, false, true, false><<<grid, 256, 0, st>>>(p);
+}
+
 }  // namespace g2s
 
 using namespace g2s;
@@ -140,4 +348,80 @@ extern "C" int g2s_raster_rgb_fwd(const float *verts, const int32_t *faces, cons
     if (faces) raster_rgb_kernel<false><<<cdiv(n, 256), 256, 0, as_stream(stream)>>>(p);
     else raster_rgb_kernel<true><<<cdiv(n, 256), 256, 0, as_stream(stream)>>>(p);
     return check_launch("g2s_raster_rgb_fwd");
+}
+
+static size_t rgb_bwd_tex_elems(int B, int n_faces, int ts, int C) { return (size_t)B * n_faces * ts * ts * ts * C; }
+
+extern "C" size_t g2s_raster_rgb_bwd_workspace_bytes(int B, int n_verts, int n_faces, int ts, int C) {
+    if (B <= 0 || n_verts <= 0 || n_faces <= 0 || ts <= 0 || C <= 0) return 0;
+    return (rgb_bwd_tex_elems(B, n_faces, ts, C) + (size_t)B * n_verts * 3) * sizeof(long long) + 256;
+}
+
+extern "C" int g2s_raster_rgb_bwd(const float *verts, const int32_t *faces, const int32_t *face_idx,
+                                  const float *bary, const float *textures, const float *grad_rgb, int B,
+                                  int n_verts, int n_faces, int S, const float *K, float orig_size, int ssaa,
+                                  int ts, int C, float eps, float *grad_textures, float *grad_verts,
+                                  void *workspace, size_t workspace_bytes, int acc_is_zero, g2s_stream_t stream) {
+    G2S_REQUIRE(verts && face_idx && bary && textures && grad_rgb, "NULL pointer argument");
+    G2S_REQUIRE(grad_textures || grad_verts, "grad_textures and grad_verts are both NULL: nothing to compute");
+    G2S_REQUIRE(B > 0 && n_verts > 0 && n_faces > 0 && S > 0, "sizes must be positive");
+    G2S_REQUIRE(ssaa == 1 || ssaa == 2, "ssaa must be 1 or 2");
+    G2S_REQUIRE(ts >= 1 && ts <= 8 && C >= 1 && C <= 4, "texture size 1..8, 1..4 channels");
+    G2S_REQUIRE(faces || (n_verts == S * S && n_faces == 2 * (S - 1) * (S - 1)),
+                "implicit topology needs S*S vertices and 2(S-1)^2 faces");
+    RgbBwdParams p{};
+    const int rc = make_cam(K, orig_size, p.cam);
+    if (rc) return rc;
+    p.verts = verts;
+    p.faces = faces;
+    p.face_idx = face_idx;
+    p.bary = bary;
+    p.tex = textures;
+    p.grad_rgb = grad_rgb;
+    p.B = B;
+    p.N = n_verts;
+    p.F = n_faces;
+    p.S = S;
+    p.is = S * ssaa;
+    p.ssaa = ssaa;
+    p.ts = ts;
+    p.C = C;
+    p.eps = eps;
+    hipStream_t st = as_stream(stream);
+    const size_t nt = rgb_bwd_tex_elems(B, n_faces, ts, C), nv = (size_t)B * n_verts * 3;
+    const bool want_t = grad_textures != nullptr, want_v = grad_verts != nullptr;
+    if (deterministic()) {
+        // float atomics would make the sums depend on the order the tiles finish in
+        const size_t need = g2s_raster_rgb_bwd_workspace_bytes(B, n_verts, n_faces, ts, C);
+        if (!workspace || workspace_bytes < need)
+            return fail(G2S_ERR_WORKSPACE, "deterministic mode: the backward needs its fixed-point workspace "
+                        "(g2s_raster_rgb_bwd_workspace_bytes = %zu bytes, got %zu)", need,
+                        workspace ? workspace_bytes : (size_t)0);
+        long long *fix = reinterpret_cast<long long *>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+        p.gtex = fix;
+        p.gver = fix + nt;
+        if (!acc_is_zero && hipMemsetAsync(fix, 0, (nt + nv) * sizeof(long long), st) != hipSuccess)
+            return fail(G2S_ERR_LAUNCH, "hipMemsetAsync(workspace) failed");
+        if (ts == 2) launch_rgb_bwd<long long, true>(p, want_t, want_v, st);
+        else launch_rgb_bwd<long long, false>(p, want_t, want_v, st);
+        if (want_t) raster_rgb_bwd_unfix<<<cdiv((long)nt, 256), 256, 0, st>>>(fix, grad_textures, (long)nt);
+        if (want_v)
+            raster_rgb_bwd_project<<<cdiv((long)B * n_verts, 256), 256, 0, st>>>(verts, grad_verts, fix + nt, p.cam,
+                                                                                  (long)B * n_verts);
+    } else {
+        p.gtex = grad_textures;
+        p.gver = grad_verts;
+        if (!acc_is_zero) {
+            if (want_t && hipMemsetAsync(grad_textures, 0, nt * sizeof(float), st) != hipSuccess)
+                return fail(G2S_ERR_LAUNCH, "hipMemsetAsync(grad_textures) failed");
+            if (want_v && hipMemsetAsync(grad_verts, 0, nv * sizeof(float), st) != hipSuccess)
+                return fail(G2S_ERR_LAUNCH, "hipMemsetAsync(grad_verts) failed");
+        }
+        if (ts == 2) launch_rgb_bwd<float, true>(p, want_t, want_v, st);
+        else launch_rgb_bwd<float, false>(p, want_t, want_v, st);
+        if (want_v)
+            raster_rgb_bwd_project<<<cdiv((long)B * n_verts, 256), 256, 0, st>>>(verts, grad_verts, nullptr, p.cam,
+                                                                                  (long)B * n_verts);
+    }
+    return check_launch("g2s_raster_rgb_bwd");
 }

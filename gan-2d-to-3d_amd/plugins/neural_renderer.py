@@ -6,9 +6,11 @@ light_intensity_directional=0., K=K, R=R, t=t, near=.., far=.., image_size=S, or
 fill_back=True, background_color=[1,1,1])` (renderer.py:47-54) and calls
 `.render_depth(vertices [B,N,3] f32, faces [B,F,3] i32) -> [B,S,S] f32` (renderer.py:120),
 differentiable w.r.t. `vertices`.  `.render_rgb(vertices, faces, textures [B,F,T,T,T,C])`
-(renderer.py:196,230,248,272,275 — the visualisation helpers) is the forward texture pass
-(g2s_raster_rgb_fwd); it returns a tensor without autograd history (the reference never
-differentiates through it; the package's silhouette-gradient kernels are not rebuilt).
+(renderer.py:196,230,248,272,275) is the texture pass (g2s_raster_rgb_fwd / g2s_raster_rgb_bwd),
+differentiable w.r.t. `textures` (exact) and `vertices`.  The vertex gradient is the gradient of the
+texture lookup with the winning face of every sample held fixed: it has NO SILHOUETTE TERM (the
+package approximates the effect of moving silhouettes with an edge-sweep heuristic that nothing here
+can pin and that is not rebuilt; `render` / `render_silhouettes` are refused for the same reason).
 
 Semantics follow SURVEY.md Appendix A (the package itself is un-vendored and un-pinned, so parity
 is checked against the oracle's restatement, not against the CUDA original):
@@ -113,6 +115,74 @@ class RenderDepthFunction(Function):
         return gv, None, None, None, None, None, None, None, None
 
 
+class RenderRgbFunction(Function):
+    """vertices (B,N,3) camera space, textures (B,F,T,T,T,C) -> rgb (B,C,S,S).  `faces` is (F,3) int32
+    or None (implicit regular grid).  Backward: g2s_raster_rgb_bwd — the adjoint of the trilinear read
+    for the textures, the derivative of the texture lookup (winners fixed, no silhouette term) for the
+    vertices; only the gradients `ctx.needs_input_grad` names are computed."""
+
+    @staticmethod
+    def forward(ctx, vertices, textures, faces, K, orig_size, image_size, anti_aliasing, fill_back, near, far,
+                background, eps):
+        verts = vertices.contiguous()
+        tex = textures.contiguous()
+        B, N, _ = verts.shape
+        S = int(image_size)
+        ssaa = 2 if anti_aliasing else 1
+        F, ts, C = tex.shape[1], tex.shape[2], tex.shape[5]
+        L = _lib.load()
+        depth = torch.empty((B, S, S), dtype=torch.float32, device=verts.device)
+        fidx = torch.empty((B, S * ssaa, S * ssaa), dtype=torch.int32, device=verts.device)
+        bary = torch.empty((B, S * ssaa, S * ssaa, 3), dtype=torch.float32, device=verts.device)
+        ws = _workspace(verts.device, L.g2s_raster_workspace_bytes(B, N, F, S))
+        Kc = (_lib.C.c_float * 9)(*K)
+        _lib.check(L.g2s_raster_depth_fwd(_lib.ptr(verts), _lib.ptr(faces), B, N, F, S, Kc, float(orig_size), ssaa,
+                                          int(bool(fill_back)), float(near), float(far),
+                                          _lib.ptr(depth), _lib.ptr(fidx), _lib.ptr(bary), _lib.ptr(ws),
+                                          ws.numel(), _lib.stream()))
+        rgb = torch.empty((B, C, S, S), dtype=torch.float32, device=verts.device)
+        _lib.check(L.g2s_raster_rgb_fwd(_lib.ptr(verts), _lib.ptr(faces), _lib.ptr(fidx), _lib.ptr(bary), _lib.ptr(tex),
+                                        B, N, F, S, ssaa, ts, C, (_lib.C.c_float * C)(*background),
+                                        float(eps), _lib.ptr(rgb), _lib.stream()))
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            ctx.save_for_backward(verts, faces, fidx, bary, tex)
+        ctx.meta = (K, float(orig_size), S, ssaa, float(eps))
+        return rgb
+
+    @staticmethod
+    def backward(ctx, grad_rgb):
+        verts, faces, fidx, bary, tex = ctx.saved_tensors
+        K, orig_size, S, ssaa, eps = ctx.meta
+        B, N, _ = verts.shape
+        F, ts, C = tex.shape[1], tex.shape[2], tex.shape[5]
+        want_v, want_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        g = grad_rgb.contiguous().float()
+        L = _lib.load()
+        Kc = (_lib.C.c_float * 9)(*K)
+        # the scatter targets must start at zero, as in RenderDepthFunction.backward: slices of the step's
+        # cleared pool when there is one (acc_is_zero = 1), else the call clears them itself
+        ws, ws_bytes, gv, gt = None, 0, None, None
+        if L.g2s_get_deterministic():
+            ws_bytes = L.g2s_raster_rgb_bwd_workspace_bytes(B, N, F, ts, C)
+            ws = _zp.take(((ws_bytes + 3) // 4,), verts.device)
+            pre = ws is not None
+            if ws is None:
+                ws = _workspace(verts.device, ws_bytes)
+            gv = torch.empty_like(verts) if want_v else None
+            gt = torch.empty_like(tex) if want_t else None
+        else:
+            gv = _zp.take(tuple(verts.shape), verts.device) if want_v else None
+            gt = _zp.take(tuple(tex.shape), verts.device) if want_t else None
+            pre = (gv is not None or not want_v) and (gt is not None or not want_t)
+            if not pre:     # one flag covers both targets: clear the pooled one again rather than split the call
+                gv = torch.empty_like(verts) if want_v else None
+                gt = torch.empty_like(tex) if want_t else None
+        _lib.check(L.g2s_raster_rgb_bwd(_lib.ptr(verts), _lib.ptr(faces), _lib.ptr(fidx), _lib.ptr(bary),
+                                        _lib.ptr(tex), _lib.ptr(g), B, N, F, S, Kc, orig_size, ssaa, ts, C, eps,
+                                        _lib.ptr(gt), _lib.ptr(gv), _lib.ptr(ws), ws_bytes, int(pre), _lib.stream()))
+        return gv, gt, None, None, None, None, None, None, None, None, None, None
+
+
 class Renderer:
     """`nr.Renderer` for camera_mode='projection' (the only mode GAN2Shape uses)."""
 
@@ -209,7 +279,11 @@ class Renderer:
         """[B, C, S, S] image of the textured mesh: rasterize with the constructor's near / far
         (renderer.py:51), read each winning face's texture cube trilinearly at perspective-corrected
         barycentric coordinates, background colour elsewhere, flip + 2x2 average.  Lighting: ambient
-        only (GAN2Shape builds the renderer with light_intensity_ambient=1, directional=0)."""
+        only (GAN2Shape builds the renderer with light_intensity_ambient=1, directional=0).
+
+        Differentiable w.r.t. `textures` and `vertices` (RenderRgbFunction): gradient of the texture
+        lookup, no silhouette term.  R, t and the ambient intensity are torch ops around the function,
+        so autograd carries them.  When neither input requires grad the result has no history."""
         K = self.K if K is None else K
         R = self.R if R is None else R
         t = self.t if t is None else t
@@ -219,42 +293,26 @@ class Renderer:
         if K is None:
             raise ValueError("camera_mode='projection' needs K")
         _lib.require_cuda(vertices, textures)
-        with torch.no_grad():
-            vertices = vertices.detach().float()
-            if self._needs_transform(R, t):
-                if R is not None:
-                    vertices = torch.matmul(vertices, R.reshape(-1, 3, 3).transpose(2, 1))
-                if t is not None:
-                    vertices = vertices + t.reshape(-1, 1, 3)
-            verts = vertices.contiguous()
-            B, N, _ = verts.shape
-            S = self.image_size
-            f = self._shared_faces(faces, N, S)
-            F = 2 * (S - 1) * (S - 1) if f is None else f.shape[0]
-            tex = textures.detach().float().contiguous()
-            if tex.dim() != 6 or tex.shape[0] != B or tex.shape[1] != F or not (tex.shape[2] == tex.shape[3] == tex.shape[4]):
-                raise ValueError(f"textures must be [B={B}, F={F}, T, T, T, C], got {tuple(tex.shape)}")
-            ts, C = tex.shape[2], tex.shape[5]
-            if self.light_intensity_ambient != 1:
-                tex = tex * float(self.light_intensity_ambient)
-            ssaa = 2 if self.anti_aliasing else 1
-            L = _lib.load()
-            depth = torch.empty((B, S, S), dtype=torch.float32, device=verts.device)
-            fidx = torch.empty((B, S * ssaa, S * ssaa), dtype=torch.int32, device=verts.device)
-            bary = torch.empty((B, S * ssaa, S * ssaa, 3), dtype=torch.float32, device=verts.device)
-            ws = _workspace(verts.device, L.g2s_raster_workspace_bytes(B, N, F, S))
-            Kc = (_lib.C.c_float * 9)(*self._host_K(K))
-            _lib.check(L.g2s_raster_depth_fwd(_lib.ptr(verts), _lib.ptr(f), B, N, F, S, Kc, float(orig_size), ssaa,
-                                              int(bool(self.fill_back)), float(self.near), float(self.far),
-                                              _lib.ptr(depth), _lib.ptr(fidx), _lib.ptr(bary), _lib.ptr(ws),
-                                              ws.numel(), _lib.stream()))
-            bg = [float(v) for v in self.background_color][:C]
-            bg += [bg[-1]] * (C - len(bg))
-            rgb = torch.empty((B, C, S, S), dtype=torch.float32, device=verts.device)
-            _lib.check(L.g2s_raster_rgb_fwd(_lib.ptr(verts), _lib.ptr(f), _lib.ptr(fidx), _lib.ptr(bary), _lib.ptr(tex),
-                                            B, N, F, S, ssaa, ts, C, (_lib.C.c_float * C)(*bg),
-                                            float(self.rasterizer_eps), _lib.ptr(rgb), _lib.stream()))
-        return rgb
+        vertices = vertices.float()
+        if self._needs_transform(R, t):
+            if R is not None:
+                vertices = torch.matmul(vertices, R.reshape(-1, 3, 3).transpose(2, 1))
+            if t is not None:
+                vertices = vertices + t.reshape(-1, 1, 3)
+        B, N, _ = vertices.shape
+        S = self.image_size
+        f = self._shared_faces(faces, N, S)
+        F = 2 * (S - 1) * (S - 1) if f is None else f.shape[0]
+        tex = textures.float()
+        if tex.dim() != 6 or tex.shape[0] != B or tex.shape[1] != F or not (tex.shape[2] == tex.shape[3] == tex.shape[4]):
+            raise ValueError(f"textures must be [B={B}, F={F}, T, T, T, C], got {tuple(tex.shape)}")
+        C = tex.shape[5]
+        if self.light_intensity_ambient != 1:
+            tex = tex * float(self.light_intensity_ambient)
+        bg = [float(v) for v in self.background_color][:C]
+        bg += [bg[-1]] * (C - len(bg))
+        return RenderRgbFunction.apply(vertices, tex, f, self._host_K(K), orig_size, S, self.anti_aliasing,
+                                       self.fill_back, self.near, self.far, tuple(bg), self.rasterizer_eps)
 
     def render(self, *a, **k):
         raise NotImplementedError("render / render_silhouettes (alpha channel, silhouette gradients) are not part "

@@ -5,9 +5,12 @@ behind `warp_canon_depth` is the libg2s kernel (through the neural_renderer drop
 that do not change results: tensors are created on `device` directly (the reference hard-codes
 .cuda()); the pixel grid, face list and rotation centre are built once; `grid_sample` gets
 `align_corners=True` explicitly (the reference targets torch 1.2 where that was the only
-behaviour).  The visualisation helpers — render_yaw, render_view, the
-grid_sample=False branch of render_given_view (renderer.py:141-277), downscale_K — go through the
-texture path of the rasterizer (`render_rgb`); their pose sweeps share one helper (`_sweep`).
+behaviour).  render_yaw, render_view, the grid_sample=False branch of
+render_given_view (renderer.py:141-277) and downscale_K go through the texture path of the
+rasterizer (`render_rgb`); their pose sweeps share one helper (`_sweep`).  That path is
+differentiable: everything around `render_rgb` is torch ops, so render_given_view(im, depth, view,
+grid_sample=False) carries gradients to `im`, `depth` and `view` (gradient of the texture lookup,
+no silhouette term — plugins/neural_renderer.py).
 """
 import math
 
@@ -186,7 +189,7 @@ class Renderer():
             self._K9 = tuple(float(v) for v in self.K[0].reshape(9).tolist())
             # like the reference, the nr.Renderer built in __init__ keeps the original intrinsics
 
-    # ------------------------------------------------------------------ texture path (visualisation)
+    # ------------------------------------------------------------------ texture path (differentiable)
     def _render_textured(self, verts, im):
         """render_rgb of the grid mesh `verts` (b, h*w, 3) coloured by `im` (b, c, h, w), clamped to
         [-1, 1] (renderer.py:196,272)."""

@@ -59,7 +59,8 @@ int g2s_get_deterministic(void);
  * them from the step's one cleared pool, zeropool.py) and the memset is skipped; it holds for that call only:
  * g2s_warp_verts_bwd / g2s_inv_warp_grid_bwd (gRt), g2s_smooth_loss_fwd (loss), g2s_shading_bwd (glight),
  * g2s_depth_head_bwd (gsum), g2s_grid_sample_bwd (gx, or the deterministic mode's fixed-point workspace),
- * g2s_raster_depth_bwd_ex (grad_verts, or its fixed-point workspace; g2s_raster_depth_bwd passes 0). */
+ * g2s_raster_depth_bwd_ex (grad_verts, or its fixed-point workspace; g2s_raster_depth_bwd passes 0),
+ * g2s_raster_rgb_bwd (grad_textures and grad_verts, or its fixed-point workspace). */
 
 /* ------------------------------------------------------------------------------------------
  * Differentiable depth rasterizer.
@@ -122,7 +123,7 @@ int g2s_raster_depth_bwd_ex(const float *verts, const int32_t *faces, const floa
                             g2s_stream_t stream);
 
 /* Texture path: nr.Renderer.render_rgb(vertices, faces, textures [B,F,ts,ts,ts,C]) as the reference's
- * visualisation helpers call it (GAN2Shape/renderer/renderer.py:196,230,248,272,275).  Forward only.
+ * helpers call it (GAN2Shape/renderer/renderer.py:196,230,248,272,275).
  * Second pass over the maps g2s_raster_depth_fwd saves (run it with the constructor's near / far,
  * renderer.py:51): trilinear read of the winning face's texture cube at perspective-corrected
  * barycentric coordinates (eps = rasterizer_eps, 1e-3 in the package), `background` (HOST pointer, C
@@ -132,6 +133,32 @@ int g2s_raster_rgb_fwd(const float *verts, const int32_t *faces, const int32_t *
                        const float *bary, const float *textures, int B, int n_verts, int n_faces, int S,
                        int ssaa, int ts, int C, const float *background, float eps, float *rgb_out,
                        g2s_stream_t stream);
+
+/* Backward of the texture pass (replaces the autograd of neural_renderer's render_rgb at the call sites above,
+ * renderer.py:265-276 render_given_view(grid_sample=False) among them): GRADIENT OF THE TEXTURE LOOKUP, NO
+ * SILHOUETTE TERM.  The winner of every raster sample (face_idx) is held fixed.
+ * grad_rgb       [B, C, S, S] gradient of rgb_out
+ * grad_textures  [B, F, ts, ts, ts, C]: adjoint of the trilinear read (exact, the forward is affine in the
+ *                textures); a reversed fill_back copy adds to the cube of its geometric face with axes 0 and 2
+ *                swapped; background samples add nothing.  NULL: not computed.
+ * grad_verts     [B, n_verts, 3]: colour -> cube coordinates t_k (zero where a clamp is active) -> barycentric
+ *                weights and vertex depths -> projected vertices (the weights are the screen-space barycentrics of
+ *                the sample centre) -> camera xyz.  The external package instead approximates the effect of moving
+ *                silhouettes with an edge-sweep heuristic that is not rebuilt here (nothing pins it).  NULL: not
+ *                computed, and its arithmetic is skipped.  Both NULL is G2S_ERR_INVALID.
+ * K, orig_size   as g2s_raster_depth_fwd; the other arguments as g2s_raster_rgb_fwd (same requirements: ts 1..8,
+ *                C 1..4, ssaa 1 or 2, implicit-topology sizes when faces is NULL).
+ * Sums use float atomics.  In deterministic mode (g2s_set_deterministic) they are 2^-40 fixed point with 64-bit
+ * integer atomics in `workspace` (>= g2s_raster_rgb_bwd_workspace_bytes bytes of device memory; range +-8.4e6,
+ * resolution 9e-13, non-finite contributions dropped) and both gradients are bit-identical from run to run; a NULL
+ * / short workspace is then G2S_ERR_WORKSPACE; otherwise the workspace is ignored.  acc_is_zero = 1: the buffers
+ * the sums go to (the workspace in deterministic mode, else every non-NULL gradient) are already zero, no memset. */
+size_t g2s_raster_rgb_bwd_workspace_bytes(int B, int n_verts, int n_faces, int ts, int C);
+int g2s_raster_rgb_bwd(const float *verts, const int32_t *faces, const int32_t *face_idx, const float *bary,
+                       const float *textures, const float *grad_rgb, int B, int n_verts, int n_faces, int S,
+                       const float *K, float orig_size, int ssaa, int ts, int C, float eps,
+                       float *grad_textures, float *grad_verts, void *workspace, size_t workspace_bytes,
+                       int acc_is_zero, g2s_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * fused bias + activation.
