@@ -34,6 +34,7 @@ SOURCES = {
     "losses.hip": [],
     "geometry.hip": ["-ffp-contract=off"],
     "grid_sample.hip": ["-ffp-contract=off"],
+    "priors.hip": ["-ffp-contract=off"],         # restates the torch expressions of priors.py operation by operation
     "groupnorm.hip": [],
     "conv_wgrad.hip": [],
     "adam.hip": [],

@@ -14,7 +14,7 @@ CONV_PLAIN, CONV_UP2, CONV_DOWN2 = 0, 1, 2
 _lib = None
 
 # name: (restype, argtypes) — exactly the declarations of include/g2s.h
-_p, _i, _f, _sz, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
+_p, _i, _f, _sz, _i64, _d = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64, C.c_double
 SIGNATURES = {
     "g2s_abi_version": (_i, []),
     "g2s_last_error": (C.c_char_p, []),
@@ -94,6 +94,11 @@ SIGNATURES = {
     "g2s_groupnorm_workspace_floats": (_sz, [_i, _i, _i, _i]),
     "g2s_groupnorm_act_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _f, _p]),
     "g2s_groupnorm_act_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
+    "g2s_prior_map": (_i, [_p, _i, _i, _i, _d, _d, _p, _p]),
+    "g2s_prior_smooth_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "g2s_prior_smooth": (_i, [_p, _i, _i, _i, _i, _d, _d, _p, _p, _sz, _p]),
+    "g2s_prior_ellipsoid_workspace_bytes": (_sz, [_i]),
+    "g2s_prior_ellipsoid": (_i, [_p, _i, _i, _d, _d, _d, _d, _p, _p, _sz, _p]),
 }
 
 

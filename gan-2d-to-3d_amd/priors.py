@@ -7,12 +7,18 @@ synthetic mask is used (benchmarks, tests).  The confidence priors take the pars
 confidence map through the same callable.
 
 Priors are maps in [near, far] (smaller = closer): `far` outside the object.
+
+Two ways to build them.  The default restates the reference on the host (CPU mask, F.conv2d,
+torch.nonzero, a copy to the device).  `PriorGenerator(..., on_device=True)` builds them with the
+kernels of csrc/priors.hip (include/g2s.h g2s_prior_*): batched over images, no host synchronisation,
+recordable in a HIP graph.
 """
 import math
 
 import torch
 import torch.nn.functional as F
 
+from . import lib as _lib
 from . import utils
 
 
@@ -31,8 +37,16 @@ class PriorGenerator():
     SMOOTH_PASSES = 3
     ELLIPSOID_RADIUS = 0.4
 
+    # g2s_prior_map kind behind each prior; the smoothed ones smooth that map
+    MAP_KINDS = {"box": 0, "masked_box": 1, "confidence": 2, "smoothed_box": 1, "smoothed_confidence": 2}
+
     def __init__(self, image_size, category, prior, noise_threshold=0.7, near=0.91, far=1.02,
-                 masking_model=None):
+                 masking_model=None, on_device=False, mask_accepts_batch=False):
+        """on_device: build the priors with libg2s (CUDA tensors only; `batch` becomes available).
+        mask_accepts_batch: `masking_model` takes a (B, 3, S, S) batch and returns (B, 1, S, S), and `batch`
+        uses it as is; else `batch` calls it once per image.  It is an argument because the callable cannot be
+        probed: one that ignores its input (a fixed mask) or broadcasts would pass a shape test on a batch
+        and return the wrong masks, and a probing call costs a forward of the caller's parsing network."""
         self._build = getattr(self, f'_{prior}_prior', None)
         if self._build is None:
             raise NotImplementedError()
@@ -40,10 +54,82 @@ class PriorGenerator():
         self.noise_threshold, self.near, self.far = noise_threshold, near, far
         self.base_prior = torch.full((1, image_size, image_size), float(far))
         self.masking_model = synthetic_mask if masking_model is None else masking_model
+        self.on_device, self.mask_accepts_batch = on_device, mask_accepts_batch
 
     def __call__(self, image, device='cuda', *args, **kwargs):
+        if self.on_device:
+            if args or kwargs:     # the host builders take none either; do not drop them silently
+                raise TypeError(f"PriorGenerator(on_device=True): unexpected arguments {args} {kwargs}")
+            return self.batch(image, device=device)
         with torch.no_grad():
             return self._build(image, *args, **kwargs).to(device)
+
+    # ---- device path (csrc/priors.hip)
+    def batch(self, images, device='cuda'):
+        """(B, S, S) priors of a (B, 3, S, S) batch, or of a list of (1, 3, S, S) images, in one set of
+        launches on the current stream; needs on_device=True.  Nothing here synchronises with the host.
+        Differences from the host path: an image whose mask has no pixel at or above the threshold, or
+        a bounding box of zero width or height, gets `far` everywhere from `ellipsoid` (the host path
+        raises or divides by zero); a constant map rescales to `near` in the smoothing passes (the
+        host path gives NaN)."""
+        if not self.on_device:
+            raise RuntimeError("PriorGenerator.batch needs on_device=True")
+        device = torch.device(device)
+        images = list(images) if isinstance(images, (list, tuple)) else images
+        if device.type != 'cuda':
+            raise RuntimeError("libg2s kernels need CUDA (ROCm) tensors; there is no CPU fallback")
+        _lib.require_cuda(*(images if isinstance(images, list) else [images]))
+        with torch.no_grad(), torch.cuda.device(device):
+            return self._build_on_device(images, device)
+
+    def _masks_on_device(self, images, device):
+        """(B, S, S) float32 contiguous masks on `device`."""
+        if isinstance(images, list):
+            masks = [self.masking_model(im if im.dim() == 4 else im[None]) for im in images]
+        elif self.mask_accepts_batch or len(images) == 1:
+            masks = [self.masking_model(images)]
+        else:
+            masks = [self.masking_model(images[i:i + 1]) for i in range(len(images))]
+        masks = [m.to(device=device, dtype=torch.float32) for m in masks]     # no-ops for fp32 device masks
+        if not masks:
+            return torch.empty(0, self.image_size, self.image_size, device=device)
+        masks = masks[0] if len(masks) == 1 else torch.cat(masks)
+        S, B = self.image_size, len(images)
+        if masks.dim() != 4 or tuple(masks.shape) != (B, 1, S, S):
+            raise ValueError(f"masking_model returned {tuple(masks.shape)}, expected {(B, 1, S, S)}")
+        return masks[:, 0].contiguous()
+
+    @staticmethod
+    def _workspace(device, nbytes):
+        """Scratch of one call, allocated PER CALL (see plugins/neural_renderer._workspace: a free-list
+        hit under the caching allocator, and a block of the graph's private pool during a capture)."""
+        return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+
+    def _build_on_device(self, images, device):
+        L, S, name = _lib.load(), self.image_size, self.prior
+        B = len(images)
+        out = torch.empty(B, S, S, dtype=torch.float32, device=device)
+        if B == 0:
+            return out
+        if name == "box":
+            _lib.check(L.g2s_prior_map(None, B, S, 0, self.noise_threshold, self.far, _lib.ptr(out), _lib.stream()))
+            return out
+        mask = self._masks_on_device(images, device)
+        if name == "ellipsoid":
+            ws = self._workspace(device, L.g2s_prior_ellipsoid_workspace_bytes(B))
+            _lib.check(L.g2s_prior_ellipsoid(_lib.ptr(mask), B, S, self.noise_threshold, self.ELLIPSOID_RADIUS,
+                                             self.near, self.far, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                             _lib.stream()))
+            return out
+        kind = self.MAP_KINDS[name]
+        _lib.check(L.g2s_prior_map(_lib.ptr(mask), B, S, kind, self.noise_threshold, self.far, _lib.ptr(out),
+                                   _lib.stream()))
+        if name.startswith("smoothed_"):
+            taps, passes = self.SMOOTH_TAPS, self.SMOOTH_PASSES
+            ws = self._workspace(device, L.g2s_prior_smooth_workspace_bytes(B, S, taps, passes))
+            _lib.check(L.g2s_prior_smooth(_lib.ptr(out), B, S, taps, passes, self.near, self.far, _lib.ptr(out),
+                                          _lib.ptr(ws), ws.numel(), _lib.stream()))   # in place: safe (g2s.h)
+        return out
 
     # ---- mask sources
     def _mask(self, image):

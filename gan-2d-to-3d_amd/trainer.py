@@ -42,7 +42,8 @@ class Trainer():
         self.capturable = capturable  # Adam(capturable=True): needed to record steps in HIP graphs
         self.prior_generator = PriorGenerator(self.image_size, self.category,
                                               model_config.get('prior_name', 'ellipsoid'),
-                                              masking_model=masking_model)
+                                              masking_model=masking_model,
+                                              on_device=model_config.get('prior_on_device', False))
         self.optim_step1 = Trainer.default_optimizer([self.model.albedo_net], lr=self.learning_rate,
                                                      capturable=capturable)
         self.optim_step2 = Trainer.default_optimizer([self.model.offset_encoder_net],
@@ -299,9 +300,23 @@ class GeneralizingTrainer2(Trainer):
         n_epochs_prior passes over the batches with a fresh Adam on the depth net."""
         optim = Trainer.default_optimizer([self.model.depth_net])
         priors = {}
-        for image, _, index in DataLoader(images_latents, batch_size=1, shuffle=False):
-            if (int(index[0]) % batch_size) % world_size == rank % world_size or world_size == 1:
-                priors[int(index[0])] = self.prior_generator(image.to(self.device), device=self.device)
+        if getattr(self.prior_generator, 'on_device', False):
+            # config `prior_on_device`: this rank's priors through the batched kernels, batch_size images per set of
+            # launches
+            mine = []
+            for k in range(len(images_latents)):
+                image, _, index = images_latents[k]
+                if (int(index) % batch_size) % world_size == rank % world_size or world_size == 1:
+                    mine.append((int(index), image))
+            for at in range(0, len(mine), batch_size):
+                chunk = mine[at:at + batch_size]
+                images = torch.stack([image for _, image in chunk]).to(self.device)
+                for (index, _), prior in zip(chunk, self.prior_generator.batch(images, device=self.device)):
+                    priors[index] = prior[None]
+        else:
+            for image, _, index in DataLoader(images_latents, batch_size=1, shuffle=False):
+                if (int(index[0]) % batch_size) % world_size == rank % world_size or world_size == 1:
+                    priors[int(index[0])] = self.prior_generator(image.to(self.device), device=self.device)
         loss = None
         for _ in range(self.n_epochs_prior):
             for images, _latents, indices in self._local_batches(images_latents, batch_size, False,

@@ -621,6 +621,45 @@ int g2s_groupnorm_act_bwd(const float *gy, const float *y, const float *x, const
                           float *workspace, int B, int C, int HW, int G, int act, float alpha,
                           g2s_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Depth priors of the depth-net pre-training (csrc/priors.hip), replacing the host-side
+ * PriorGenerator of GAN2Shape/priors.py:7-107 (a CPU mask, three F.conv2d passes with a global
+ * min / max between them, torch.nonzero for the bounding box, a copy back to the device).
+ * mask, x, out [B, S, S] f32; every image is independent (each min / max / bounding box is per image);
+ * 1 <= S <= 2048, B <= 65535, B = 0 is a no-op that returns G2S_OK.  The scalars are the doubles the
+ * reference's Python holds; each is rounded to fp32 where torch rounds it, so that the maps restate the
+ * torch expressions operation by operation.  Nothing synchronises: all calls can be recorded in a HIP
+ * graph.  Results are bit-reproducible from run to run, whatever g2s_set_deterministic says (fixed
+ * summation order; min / max through integer atomics).  In-place use (out == mask, out == x) is safe.
+ *
+ *   g2s_prior_map   kind 0 box:        1 inside the centred 0.8 S x 0.5 S box, else 0 (mask unused, may be NULL)
+ *                   kind 1 masked_box: far - far * ((m' - t) / (1 - t)), m' = m < t ? 0 : m  (below the
+ *                                      threshold that is far * (1 + t / (1 - t)), as in the reference)
+ *                   kind 2 confidence: far - far * m
+ *   g2s_prior_smooth  `passes` x { valid taps x taps box filter, every tap 1 / taps; per-image min lo and
+ *                   max hi; near + (v - lo) * (far - near) / (hi - lo); border of width taps / 2 = far }.
+ *                   Each output is summed directly (taps row taps, then taps column taps): no running
+ *                   window, the rounding error does not grow with S.  taps odd and <= S, passes >= 0
+ *                   (0: out = x), near < far.  A constant filtered map (hi == lo, where the host
+ *                   expression is 0 / 0 = NaN) rescales to `near`.
+ *                   workspace: >= g2s_prior_smooth_workspace_bytes(B, S, taps, passes) bytes, scratch of one call.
+ *   g2s_prior_ellipsoid  spherical cap of `radius` over the bounding box (max_y, min_y, max_x, min_x) of
+ *                   mask >= threshold, reduced on the device: depth near at the centre, far at the rim and
+ *                   outside.  The host path raises on an empty mask; this one cannot without a
+ *                   synchronisation: an image with no pixel at or above the threshold, or whose box has
+ *                   zero width or zero height, gets `far` everywhere.  radius > 0, near < far <= near + 2 radius.
+ *                   workspace: >= g2s_prior_ellipsoid_workspace_bytes(B) bytes.
+ * A NULL / short workspace is G2S_ERR_WORKSPACE; every check precedes the first launch.
+ * ---------------------------------------------------------------------------------------- */
+int g2s_prior_map(const float *mask, int B, int S, int kind, double threshold, double far, float *out,
+                  g2s_stream_t stream);
+size_t g2s_prior_smooth_workspace_bytes(int B, int S, int taps, int passes);
+int g2s_prior_smooth(const float *x, int B, int S, int taps, int passes, double near, double far, float *out,
+                     void *workspace, size_t workspace_bytes, g2s_stream_t stream);
+size_t g2s_prior_ellipsoid_workspace_bytes(int B);
+int g2s_prior_ellipsoid(const float *mask, int B, int S, double threshold, double radius, double near,
+                        double far, float *out, void *workspace, size_t workspace_bytes, g2s_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
