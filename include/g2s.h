@@ -43,7 +43,8 @@ const char *g2s_last_error(void);
 /* Reproducible launches (no reference counterpart: torch.use_deterministic_algorithms is the
  * analogue a maintainer would reach for).  on = 1: every convolution launch of the process takes a
  * partition in which ONE workgroup owns each output element — direct kernel split-K 1
- * (csrc/modconv.hip), weight-gradient GEMM without its pixel split (csrc/conv_wgrad_core.h),
+ * (conv_launch in csrc/modconv.hip, for the fp32 kernel and the fp16-operand one of csrc/modconv_f16.hip),
+ * weight-gradient GEMM without its pixel split (csrc/conv_wgrad_core.h),
  * Winograd split-K / stream-K only with stored slices (workspace given), else whole tiles — so the
  * forward values of every network are bit-identical from run to run and independent of how many
  * workgroups race.  Slower (small layers no longer fill 256 CUs); results differ from the default

@@ -385,6 +385,38 @@ def test_modconv_f16_operands_vs_oracle(L, B, cin, cout, H, k, mode, transpose):
     assert np.linalg.norm(got - exp) <= 1e-3 * np.linalg.norm(exp)
 
 
+@pytest.mark.parametrize("B,cin,cout,H,k,alpha,gain", [
+    (4, 128, 128, 64, 3, 0.2, 2 ** 0.5),    # 64x64 tiles, quad form, epilogue in the kernel
+    (2, 64, 256, 128, 3, 0.0, 1.0),         # 128x128 tiles, quad form, epilogue in the kernel
+    (4, 128, 70, 64, 1, 0.2, 2 ** 0.5),     # 1x1: the polyphase body; 70 channels: a partial row tile
+    (2, 256, 128, 16, 3, 0.2, 2 ** 0.5)])   # few tiles: split-K, bias + activation as the second launch
+def test_conv_bias_act_f16_operands_vs_oracle(L, B, cin, cout, H, k, alpha, gain):
+    """conv + bias + leaky-ReLU on the fp16-operand kernel (conv_bias_act under OPERANDS = "f16": the frozen
+    discriminator and VGG trunk of config 5) against the fp32 oracle, at the bounds of
+    test_modconv_f16_operands_vs_oracle: the bias adds no rounding of its own and the activation
+    (slopes <= gain, applied to output and rms alike) does not widen the relative error."""
+    from gan2shape_amd import modconv as mc
+    rng = np.random.default_rng(B + cin + cout + H + k)
+    x = rng.standard_normal((B, cin, H, H)).astype(np.float32)
+    w = (rng.standard_normal((cout, cin, k, k)) / math.sqrt(cin * k * k)).astype(np.float32)
+    b = rng.standard_normal(cout).astype(np.float32)
+    pre = expected_modconv(x, w, None, None, PLAIN, 0) + b[None, :, None, None]
+    exp = (np.where(pre > 0, pre, pre * alpha) * gain).astype(np.float32)
+    saved = mc.OPERANDS
+    try:
+        mc.OPERANDS = "f16"
+        y = mc.conv_bias_act(dev(x), dev(w), dev(b), PLAIN, alpha, gain)
+    finally:
+        mc.OPERANDS = saved
+    got = y.cpu().numpy()
+    assert got.shape == exp.shape
+    rms = float(np.sqrt((exp.astype(np.float64) ** 2).mean()))
+    print("f16 bias+act: max err", np.abs(got - exp).max(), "rms", rms, "norm ratio",
+          np.linalg.norm(got - exp) / np.linalg.norm(exp))
+    assert np.abs(got - exp).max() <= 4e-3 * rms, (np.abs(got - exp).max(), rms)
+    assert np.linalg.norm(got - exp) <= 1e-3 * np.linalg.norm(exp)
+
+
 # ----------------------------------------------------------------------------- fromRGB: the thin 1x1 path
 @pytest.mark.parametrize("B,cin,cout,H,W", [(8, 3, 128, 128, 128), (5, 4, 24, 120, 132), (3, 1, 40, 160, 140)])
 def test_thin_1x1_path_vs_oracle_and_mfma(L, B, cin, cout, H, W):
