@@ -20,6 +20,7 @@ SOURCES = {
     "api.hip": [],
     "raster.hip": ["-ffp-contract=off"],  # bit-parity with the oracle's unfused arithmetic
     "raster_rgb.hip": ["-ffp-contract=off"],
+    "face_light.hip": ["-ffp-contract=off"],     # forward and backward agree on the sign of dot(n, direction)
     "fused_bias_act.hip": [],
     "upfirdn2d.hip": [],
     "modconv.hip": [],

@@ -13,6 +13,11 @@
 // samples take the background colour, then the same vertical flip + 2x2 average as the depth map.
 // Semantics follow the external neural_renderer package as recalled in SURVEY.md Appendix A
 // (PARITY UNPINNED, like the depth path); the oracle restates them independently on the CPU.
+//
+// g2s_raster_rgba_fwd / g2s_raster_rgba_bwd are the superset nr.Renderer.render needs: a per-face light factor
+// (face_light.hip, indexed by the winner id) multiplies the sample's colour before background selection, and
+// alpha is the share of a pixel's samples that have a winner.  The unlit entry points call the same launchers
+// with light = alpha_out = grad_light = NULL and run the same template instances as before.
 #include "g2s_common.h"
 #include "raster_core.h"
 #include "raster_scatter.h"
@@ -29,15 +34,19 @@ struct RgbParams {
     int B, N, F, S, is, ssaa, ts, C;
     float eps;
     float bg[4];
+    const float *light;      // [B, Ftot, 3] or NULL (EXTRA instances only; C == 3)
+    float *alpha;            // [B, S, S] or NULL (EXTRA instances only)
+    int Ftot;                // F * (1 + fill_back)
 };
 
-template <bool IMPLICIT>
-__device__ __forceinline__ void sample_colour(const RgbParams &p, int b, int yi, int xi, float col[4]) {
+// EXTRA: the instances of g2s_raster_rgba_fwd (light and / or alpha).  Returns whether the sample has a winner.
+template <bool IMPLICIT, bool EXTRA>
+__device__ __forceinline__ bool sample_colour(const RgbParams &p, int b, int yi, int xi, float col[4]) {
     const size_t si = ((size_t)b * p.is + yi) * p.is + xi;
     const int fn = p.face_idx[si];
     if (fn < 0) {
         for (int c = 0; c < p.C; c++) col[c] = p.bg[c];
-        return;
+        return false;
     }
     const int g = fn % p.F;
     const bool rev = fn >= p.F;
@@ -88,24 +97,44 @@ __device__ __forceinline__ void sample_colour(const RgbParams &p, int b, int yi,
         const int isc = rev ? (idx[2] * ts + idx[1]) * ts + idx[0] : (idx[0] * ts + idx[1]) * ts + idx[2];
         for (int c = 0; c < p.C; c++) col[c] += wt * tex[(size_t)isc * p.C + c];
     }
+    if (EXTRA && p.light) {
+        const float *l = p.light + ((size_t)b * p.Ftot + min(fn, p.Ftot - 1)) * 3;
+        for (int c = 0; c < 3; c++) col[c] *= l[c];
+    }
+    return true;
 }
 
-template <bool IMPLICIT>
+template <bool IMPLICIT, bool EXTRA>
 __global__ void raster_rgb_kernel(RgbParams p) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)p.B * p.S * p.S) return;
     const int b = (int)(i / ((long)p.S * p.S));
     const int r = (int)((i / p.S) % p.S), c0 = (int)(i % p.S);
     float sum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    int covered = 0;
     for (int dy = 0; dy < p.ssaa; dy++)
         for (int dx = 0; dx < p.ssaa; dx++) {
             const int yi = p.is - 1 - (r * p.ssaa + dy);   // row of the (unflipped) raster
             float col[4];
-            sample_colour<IMPLICIT>(p, b, yi, c0 * p.ssaa + dx, col);
+            if (sample_colour<IMPLICIT, EXTRA>(p, b, yi, c0 * p.ssaa + dx, col)) covered++;
             for (int c = 0; c < p.C; c++) sum[c] += col[c];
         }
     const float inv = 1.0f / (float)(p.ssaa * p.ssaa);
     for (int c = 0; c < p.C; c++) p.out[(((size_t)b * p.C + c) * p.S + r) * p.S + c0] = sum[c] * inv;
+    if (EXTRA && p.alpha) p.alpha[((size_t)b * p.S + r) * p.S + c0] = (float)covered * inv;
+}
+
+// Alpha alone (nr.Renderer.render_silhouettes): no texture is read.
+__global__ void raster_alpha_kernel(const int32_t *face_idx, float *alpha, int B, int S, int ssaa) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * S * S) return;
+    const int b = (int)(i / ((long)S * S));
+    const int r = (int)((i / S) % S), c0 = (int)(i % S), is = S * ssaa;
+    int covered = 0;
+    for (int dy = 0; dy < ssaa; dy++)
+        for (int dx = 0; dx < ssaa; dx++)
+            if (face_idx[((size_t)b * is + (is - 1 - (r * ssaa + dy))) * is + c0 * ssaa + dx] >= 0) covered++;
+    alpha[i] = (float)covered * (1.0f / (float)(ssaa * ssaa));
 }
 
 // ---------------------------------------------------------------------------------- backward
@@ -121,6 +150,9 @@ struct RgbBwdParams {
     Cam cam;
     void *gtex;  // [B, F, ts, ts, ts, C] sums: float, or 2^-40 fixed point in deterministic mode
     void *gver;  // [B, N, 3] sums of (g_u, g_v, g_z) of the projected vertices, same two forms
+    const float *light;  // [B, Ftot, 3] (LIT instances only; C == 3)
+    void *glight;        // [B, Ftot, 3] sums, same two forms, or NULL (LIT instances only)
+    int Ftot;            // F * (1 + fill_back)
 };
 
 // One wave per 8x8-sample tile (4 tiles per workgroup), lane = raster sample, as raster_bwd_samples.
@@ -134,7 +166,11 @@ struct RgbBwdParams {
 //             fi[3k+1] dy_l) (derivative of the inverse vertex matrix of face_inverse); the lookup position
 //             comes from the saved weights, so that forward and backward agree on cell and clamp state.
 //             Nine partials per sample, merged and scattered like the depth backward's.
-template <typename ACC, bool WANT_T, bool WANT_V, bool MERGE>
+//   light     (LIT: the forward multiplied the sample's colour by light[b, winner]) the incoming colour gradient
+//             is scaled by the light for the two gradients above; the light's own gradient is the sum over the
+//             winner's samples of grad_colour * unlit colour, three partials per sample that same-face
+//             neighbours merge like the others before the atomics.
+template <typename ACC, bool WANT_T, bool WANT_V, bool MERGE, bool LIT>
 __global__ __launch_bounds__(256) void raster_rgb_bwd_samples(RgbBwdParams p) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int tiles_side = (p.is + TILE - 1) / TILE;
@@ -203,6 +239,31 @@ __global__ __launch_bounds__(256) void raster_rgb_bwd_samples(RgbBwdParams p) {
         return rev ? (idx[2] * ts + idx[1]) * ts + idx[0] : (idx[0] * ts + idx[1]) * ts + idx[2];
     };
     const size_t cube = ((size_t)b * p.F + gidx) * ts * ts * ts * p.C;
+
+    if (LIT) {
+        float lp[3] = {0.0f, 0.0f, 0.0f};
+        if (fn >= 0) {
+            if (p.glight) {  // grad_colour * unlit colour: the forward's trilinear read again
+                for (int pn = 0; pn < 8; pn++) {
+                    float wt = 1.0f;
+                    for (int k = 0; k < 3; k++) wt *= ((pn >> k) & 1) ? tf[k] : 1.0f - tf[k];
+                    const float *tx = p.tex + cube + (size_t)cell(pn) * 3;
+                    for (int c = 0; c < 3; c++) lp[c] += wt * tx[c];
+                }
+                for (int c = 0; c < 3; c++) lp[c] *= g[c];
+            }
+            const float *l = p.light + ((size_t)b * p.Ftot + min(fn, p.Ftot - 1)) * 3;
+            for (int c = 0; c < 3; c++) g[c] *= l[c];
+        }
+        if (p.glight) {  // uniform: every lane takes part in the shuffles
+            int fl = fn;
+            merge_same_face(lp, fl, lane);
+            if (fl >= 0 && fl < p.Ftot) {
+                ACC *dst = reinterpret_cast<ACC *>(p.glight) + ((size_t)b * p.Ftot + fl) * 3;
+                for (int c = 0; c < 3; c++) acc_add(dst + c, lp[c]);
+            }
+        }
+    }
 
     if (WANT_T) {
         ACC *const gt = reinterpret_cast<ACC *>(p.gtex);
@@ -304,30 +365,41 @@ __global__ __launch_bounds__(256) void raster_rgb_bwd_unfix(const long long *fix
     if (i < n) out[i] = from_fix(fix[i]);
 }
 
-template <typename ACC, bool MERGE>
-static void launch_rgb_bwd(const RgbBwdParams &p, bool want_t, bool want_v, hipStream_t st) {
+template <typename ACC, bool MERGE, bool LIT>
+static void launch_rgb_bwd_lit(const RgbBwdParams &p, bool want_t, bool want_v, hipStream_t st) {
     const int tiles = cdiv(p.is, TILE) * cdiv(p.is, TILE);
     const dim3 grid(cdiv(tiles, 4), p.B);
-    if (want_t && want_v) raster_rgb_bwd_samples<ACC, true, true, MERGE><<<grid, 256, 0, st>>>(p);
-    else if (want_t) raster_rgb_bwd_samples<ACC, true, false, MERGE><<<grid, 256, 0, st>>>(p);
-    else raster_rgb_bwd_samples<ACC, false, true, false><<<grid, 256, 0, st>>>(p);
+    if (want_t && want_v) raster_rgb_bwd_samples<ACC, true, true, MERGE, LIT><<<grid, 256, 0, st>>>(p);
+    else if (want_t) raster_rgb_bwd_samples<ACC, true, false, MERGE, LIT><<<grid, 256, 0, st>>>(p);
+    else raster_rgb_bwd_samples<ACC, false, true, false, LIT><<<grid, 256, 0, st>>>(p);
+}
+
+template <typename ACC, bool MERGE>
+static void launch_rgb_bwd(const RgbBwdParams &p, bool want_t, bool want_v, hipStream_t st) {
+    if (p.light) launch_rgb_bwd_lit<ACC, MERGE, true>(p, want_t, want_v, st);
+    else launch_rgb_bwd_lit<ACC, MERGE, false>(p, want_t, want_v, st);
 }
 
 }  // namespace g2s
 
 using namespace g2s;
 
-extern "C" int g2s_raster_rgb_fwd(const float *verts, const int32_t *faces, const int32_t *face_idx,
-                                  const float *bary, const float *textures, int B, int n_verts, int n_faces,
-                                  int S, int ssaa, int ts, int C, const float *background, float eps,
-                                  float *rgb_out, g2s_stream_t stream) {
+// The one host launcher of the forward kernel; `who` names the entry point in a launch error.
+static int rgb_fwd(const char *who, const float *verts, const int32_t *faces, const int32_t *face_idx,
+                   const float *bary, const float *textures, const float *light, int B, int n_verts, int n_faces,
+                   int S, int ssaa, int ts, int C, int fill_back, const float *background, float eps, float *rgb_out,
+                   float *alpha_out, g2s_stream_t stream) {
     G2S_REQUIRE(verts && face_idx && bary && textures && rgb_out && background, "NULL pointer argument");
     G2S_REQUIRE(B > 0 && n_verts > 0 && n_faces > 0 && S > 0, "sizes must be positive");
     G2S_REQUIRE(ssaa == 1 || ssaa == 2, "ssaa must be 1 or 2");
     G2S_REQUIRE(ts >= 1 && ts <= 8 && C >= 1 && C <= 4, "texture size 1..8, 1..4 channels");
     G2S_REQUIRE(faces || (n_verts == S * S && n_faces == 2 * (S - 1) * (S - 1)),
                 "implicit topology needs S*S vertices and 2(S-1)^2 faces");
+    G2S_REQUIRE(!light || C == 3, "a light factor needs 3 channels");
     RgbParams p{};
+    p.light = light;
+    p.alpha = alpha_out;
+    p.Ftot = n_faces * (fill_back ? 2 : 1);
     p.verts = verts;
     p.faces = faces;
     p.face_idx = face_idx;
@@ -345,9 +417,36 @@ extern "C" int g2s_raster_rgb_fwd(const float *verts, const int32_t *faces, cons
     p.eps = eps;
     for (int c = 0; c < C; c++) p.bg[c] = background[c];
     const long n = (long)B * S * S;
-    if (faces) raster_rgb_kernel<false><<<cdiv(n, 256), 256, 0, as_stream(stream)>>>(p);
-    else raster_rgb_kernel<true><<<cdiv(n, 256), 256, 0, as_stream(stream)>>>(p);
-    return check_launch("g2s_raster_rgb_fwd");
+    const bool extra = light || alpha_out;
+    if (faces && extra) raster_rgb_kernel<false, true><<<cdiv(n, 256), 256, 0, as_stream(stream)>>>(p);
+    else if (faces) raster_rgb_kernel<false, false><<<cdiv(n, 256), 256, 0, as_stream(stream)>>>(p);
+    else if (extra) raster_rgb_kernel<true, true><<<cdiv(n, 256), 256, 0, as_stream(stream)>>>(p);
+    else raster_rgb_kernel<true, false><<<cdiv(n, 256), 256, 0, as_stream(stream)>>>(p);
+    return check_launch(who);
+}
+
+extern "C" int g2s_raster_rgb_fwd(const float *verts, const int32_t *faces, const int32_t *face_idx,
+                                  const float *bary, const float *textures, int B, int n_verts, int n_faces,
+                                  int S, int ssaa, int ts, int C, const float *background, float eps,
+                                  float *rgb_out, g2s_stream_t stream) {
+    return rgb_fwd("g2s_raster_rgb_fwd", verts, faces, face_idx, bary, textures, nullptr, B, n_verts, n_faces, S, ssaa,
+                   ts, C, 0, background, eps, rgb_out, nullptr, stream);
+}
+
+extern "C" int g2s_raster_rgba_fwd(const float *verts, const int32_t *faces, const int32_t *face_idx,
+                                   const float *bary, const float *textures, const float *light, int B, int n_verts,
+                                   int n_faces, int S, int ssaa, int ts, int C, int fill_back,
+                                   const float *background, float eps, float *rgb_out, float *alpha_out,
+                                   g2s_stream_t stream) {
+    if (!textures && !rgb_out && !light) {  // alpha alone: no texture pass
+        G2S_REQUIRE(face_idx && alpha_out, "NULL pointer argument");
+        G2S_REQUIRE(B > 0 && S > 0, "sizes must be positive");
+        G2S_REQUIRE(ssaa == 1 || ssaa == 2, "ssaa must be 1 or 2");
+        raster_alpha_kernel<<<cdiv((long)B * S * S, 256), 256, 0, as_stream(stream)>>>(face_idx, alpha_out, B, S, ssaa);
+        return check_launch("g2s_raster_rgba_fwd");
+    }
+    return rgb_fwd("g2s_raster_rgba_fwd", verts, faces, face_idx, bary, textures, light, B, n_verts, n_faces, S, ssaa,
+                   ts, C, fill_back, background, eps, rgb_out, alpha_out, stream);
 }
 
 static size_t rgb_bwd_tex_elems(int B, int n_faces, int ts, int C) { return (size_t)B * n_faces * ts * ts * ts * C; }
@@ -357,12 +456,20 @@ extern "C" size_t g2s_raster_rgb_bwd_workspace_bytes(int B, int n_verts, int n_f
     return (rgb_bwd_tex_elems(B, n_faces, ts, C) + (size_t)B * n_verts * 3) * sizeof(long long) + 256;
 }
 
-extern "C" int g2s_raster_rgb_bwd(const float *verts, const int32_t *faces, const int32_t *face_idx,
-                                  const float *bary, const float *textures, const float *grad_rgb, int B,
-                                  int n_verts, int n_faces, int S, const float *K, float orig_size, int ssaa,
-                                  int ts, int C, float eps, float *grad_textures, float *grad_verts,
-                                  void *workspace, size_t workspace_bytes, int acc_is_zero, g2s_stream_t stream) {
+extern "C" size_t g2s_raster_rgba_bwd_workspace_bytes(int B, int n_verts, int n_faces, int ts, int C, int fill_back) {
+    const size_t unlit = g2s_raster_rgb_bwd_workspace_bytes(B, n_verts, n_faces, ts, C);
+    return unlit ? unlit + (size_t)B * n_faces * (fill_back ? 2 : 1) * 3 * sizeof(long long) : 0;
+}
+
+// The one host launcher of the backward kernels; `who` names the entry point in its messages.
+static int rgb_bwd(const char *who, const float *verts, const int32_t *faces, const int32_t *face_idx,
+                   const float *bary, const float *textures, const float *light, const float *grad_rgb, int B,
+                   int n_verts, int n_faces, int S, const float *K, float orig_size, int ssaa, int ts, int C,
+                   int fill_back, float eps, float *grad_textures, float *grad_verts, float *grad_light,
+                   void *workspace, size_t workspace_bytes, int acc_is_zero, g2s_stream_t stream) {
     G2S_REQUIRE(verts && face_idx && bary && textures && grad_rgb, "NULL pointer argument");
+    G2S_REQUIRE(!light || C == 3, "a light factor needs 3 channels");
+    G2S_REQUIRE(light || !grad_light, "grad_light needs light");
     G2S_REQUIRE(grad_textures || grad_verts, "grad_textures and grad_verts are both NULL: nothing to compute");
     G2S_REQUIRE(B > 0 && n_verts > 0 && n_faces > 0 && S > 0, "sizes must be positive");
     G2S_REQUIRE(ssaa == 1 || ssaa == 2, "ssaa must be 1 or 2");
@@ -387,31 +494,39 @@ extern "C" int g2s_raster_rgb_bwd(const float *verts, const int32_t *faces, cons
     p.ts = ts;
     p.C = C;
     p.eps = eps;
+    p.light = light;
+    p.Ftot = n_faces * (fill_back ? 2 : 1);
     hipStream_t st = as_stream(stream);
     const size_t nt = rgb_bwd_tex_elems(B, n_faces, ts, C), nv = (size_t)B * n_verts * 3;
+    const size_t nl = grad_light ? (size_t)B * p.Ftot * 3 : 0;
     const bool want_t = grad_textures != nullptr, want_v = grad_verts != nullptr;
     if (deterministic()) {
         // float atomics would make the sums depend on the order the tiles finish in
-        const size_t need = g2s_raster_rgb_bwd_workspace_bytes(B, n_verts, n_faces, ts, C);
+        const size_t need = g2s_raster_rgb_bwd_workspace_bytes(B, n_verts, n_faces, ts, C) + nl * sizeof(long long);
         if (!workspace || workspace_bytes < need)
             return fail(G2S_ERR_WORKSPACE, "deterministic mode: the backward needs its fixed-point workspace "
-                        "(g2s_raster_rgb_bwd_workspace_bytes = %zu bytes, got %zu)", need,
+                        "(%s_workspace_bytes = %zu bytes, got %zu)", who, need,
                         workspace ? workspace_bytes : (size_t)0);
         long long *fix = reinterpret_cast<long long *>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
         p.gtex = fix;
         p.gver = fix + nt;
-        if (!acc_is_zero && hipMemsetAsync(fix, 0, (nt + nv) * sizeof(long long), st) != hipSuccess)
+        p.glight = grad_light ? fix + nt + nv : nullptr;
+        if (!acc_is_zero && hipMemsetAsync(fix, 0, (nt + nv + nl) * sizeof(long long), st) != hipSuccess)
             return fail(G2S_ERR_LAUNCH, "hipMemsetAsync(workspace) failed");
         if (ts == 2) launch_rgb_bwd<long long, true>(p, want_t, want_v, st);
         else launch_rgb_bwd<long long, false>(p, want_t, want_v, st);
         if (want_t) raster_rgb_bwd_unfix<<<cdiv((long)nt, 256), 256, 0, st>>>(fix, grad_textures, (long)nt);
+        if (grad_light) raster_rgb_bwd_unfix<<<cdiv((long)nl, 256), 256, 0, st>>>(fix + nt + nv, grad_light, (long)nl);
         if (want_v)
             raster_rgb_bwd_project<<<cdiv((long)B * n_verts, 256), 256, 0, st>>>(verts, grad_verts, fix + nt, p.cam,
                                                                                   (long)B * n_verts);
     } else {
         p.gtex = grad_textures;
         p.gver = grad_verts;
+        p.glight = grad_light;
         if (!acc_is_zero) {
+            if (grad_light && hipMemsetAsync(grad_light, 0, nl * sizeof(float), st) != hipSuccess)
+                return fail(G2S_ERR_LAUNCH, "hipMemsetAsync(grad_light) failed");
             if (want_t && hipMemsetAsync(grad_textures, 0, nt * sizeof(float), st) != hipSuccess)
                 return fail(G2S_ERR_LAUNCH, "hipMemsetAsync(grad_textures) failed");
             if (want_v && hipMemsetAsync(grad_verts, 0, nv * sizeof(float), st) != hipSuccess)
@@ -423,5 +538,26 @@ extern "C" int g2s_raster_rgb_bwd(const float *verts, const int32_t *faces, cons
             raster_rgb_bwd_project<<<cdiv((long)B * n_verts, 256), 256, 0, st>>>(verts, grad_verts, nullptr, p.cam,
                                                                                   (long)B * n_verts);
     }
-    return check_launch("g2s_raster_rgb_bwd");
+    return check_launch(who);
+}
+
+extern "C" int g2s_raster_rgb_bwd(const float *verts, const int32_t *faces, const int32_t *face_idx,
+                                  const float *bary, const float *textures, const float *grad_rgb, int B,
+                                  int n_verts, int n_faces, int S, const float *K, float orig_size, int ssaa,
+                                  int ts, int C, float eps, float *grad_textures, float *grad_verts,
+                                  void *workspace, size_t workspace_bytes, int acc_is_zero, g2s_stream_t stream) {
+    return rgb_bwd("g2s_raster_rgb_bwd", verts, faces, face_idx, bary, textures, nullptr, grad_rgb, B, n_verts, n_faces,
+                   S, K, orig_size, ssaa, ts, C, 0, eps, grad_textures, grad_verts, nullptr, workspace, workspace_bytes,
+                   acc_is_zero, stream);
+}
+
+extern "C" int g2s_raster_rgba_bwd(const float *verts, const int32_t *faces, const int32_t *face_idx,
+                                   const float *bary, const float *textures, const float *light,
+                                   const float *grad_rgb, int B, int n_verts, int n_faces, int S, const float *K,
+                                   float orig_size, int ssaa, int ts, int C, int fill_back, float eps,
+                                   float *grad_textures, float *grad_verts, float *grad_light, void *workspace,
+                                   size_t workspace_bytes, int acc_is_zero, g2s_stream_t stream) {
+    return rgb_bwd("g2s_raster_rgba_bwd", verts, faces, face_idx, bary, textures, light, grad_rgb, B, n_verts, n_faces,
+                   S, K, orig_size, ssaa, ts, C, fill_back, eps, grad_textures, grad_verts, grad_light, workspace,
+                   workspace_bytes, acc_is_zero, stream);
 }

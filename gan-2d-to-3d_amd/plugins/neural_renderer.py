@@ -10,7 +10,12 @@ differentiable w.r.t. `vertices`.  `.render_rgb(vertices, faces, textures [B,F,T
 differentiable w.r.t. `textures` (exact) and `vertices`.  The vertex gradient is the gradient of the
 texture lookup with the winning face of every sample held fixed: it has NO SILHOUETTE TERM (the
 package approximates the effect of moving silhouettes with an edge-sweep heuristic that nothing here
-can pin and that is not rebuilt; `render` / `render_silhouettes` are refused for the same reason).
+can pin and that is not rebuilt).  `.render(vertices, faces, textures) -> (rgb, depth, alpha)` returns
+all three from ONE rasterization (RenderFunction: g2s_raster_depth_fwd, g2s_face_light_fwd when lit,
+g2s_raster_rgba_fwd); rgb and depth are differentiable as in render_rgb / render_depth, the per-face
+light (ambient + directional, nr.lighting) is differentiable w.r.t. the vertices, and ALPHA CARRIES NO
+GRADIENT, for the reason above.  `.render_silhouettes(vertices, faces) -> alpha` is that alpha alone,
+without a texture pass and without a gradient.
 
 Semantics follow SURVEY.md Appendix A (the package itself is un-vendored and un-pinned, so parity
 is checked against the oracle's restatement, not against the CUDA original):
@@ -183,6 +188,132 @@ class RenderRgbFunction(Function):
         return gv, gt, None, None, None, None, None, None, None, None, None, None
 
 
+class RenderFunction(Function):
+    """nr.Renderer.render: vertices (B,N,3) camera space, textures (B,F,T,T,T,C) -> rgb (B,C,S,S), depth (B,S,S),
+    alpha (B,S,S) from ONE rasterization.  `light` is None (unlit: the texture pass of RenderRgbFunction) or the
+    host triple (ambient rgb, directional rgb, direction) of g2s_face_light_fwd, which needs C == 3.
+    Backward: depth path (g2s_raster_depth_bwd_ex), texture path (g2s_raster_rgba_bwd, colour gradient scaled by
+    the light) and light path (grad_light of the texture path through g2s_face_light_bwd) summed into one
+    grad_verts; alpha is non-differentiable (no silhouette term)."""
+
+    @staticmethod
+    def forward(ctx, vertices, textures, faces, K, orig_size, image_size, anti_aliasing, fill_back, near, far,
+                background, eps, light):
+        verts = vertices.contiguous()
+        tex = textures.contiguous()
+        B, N, _ = verts.shape
+        S = int(image_size)
+        ssaa = 2 if anti_aliasing else 1
+        F, ts, C = tex.shape[1], tex.shape[2], tex.shape[5]
+        fb = int(bool(fill_back))
+        L = _lib.load()
+        st = _lib.stream()
+        depth = torch.empty((B, S, S), dtype=torch.float32, device=verts.device)
+        fidx = torch.empty((B, S * ssaa, S * ssaa), dtype=torch.int32, device=verts.device)
+        bary = torch.empty((B, S * ssaa, S * ssaa, 3), dtype=torch.float32, device=verts.device)
+        ws = _workspace(verts.device, L.g2s_raster_workspace_bytes(B, N, F, S))
+        Kc = (_lib.C.c_float * 9)(*K)
+        _lib.check(L.g2s_raster_depth_fwd(_lib.ptr(verts), _lib.ptr(faces), B, N, F, S, Kc, float(orig_size), ssaa,
+                                          fb, float(near), float(far), _lib.ptr(depth), _lib.ptr(fidx),
+                                          _lib.ptr(bary), _lib.ptr(ws), ws.numel(), st))
+        lit = None
+        if light is not None:
+            lit = torch.empty((B, F * (1 + fb), 3), dtype=torch.float32, device=verts.device)
+            f3 = _lib.C.c_float * 3
+            _lib.check(L.g2s_face_light_fwd(_lib.ptr(verts), _lib.ptr(faces), B, N, F, S, fb, f3(*light[0]),
+                                            f3(*light[1]), f3(*light[2]), _lib.ptr(lit), st))
+        rgb = torch.empty((B, C, S, S), dtype=torch.float32, device=verts.device)
+        alpha = torch.empty((B, S, S), dtype=torch.float32, device=verts.device)
+        _lib.check(L.g2s_raster_rgba_fwd(_lib.ptr(verts), _lib.ptr(faces), _lib.ptr(fidx), _lib.ptr(bary),
+                                         _lib.ptr(tex), _lib.ptr(lit), B, N, F, S, ssaa, ts, C, fb,
+                                         (_lib.C.c_float * C)(*background), float(eps), _lib.ptr(rgb),
+                                         _lib.ptr(alpha), st))
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            ctx.save_for_backward(verts, faces, fidx, bary, tex, lit)
+        ctx.meta = (K, float(orig_size), S, ssaa, float(eps), fb, light)
+        ctx.mark_non_differentiable(alpha)
+        ctx.set_materialize_grads(False)
+        return rgb, depth, alpha
+
+    @staticmethod
+    def backward(ctx, grad_rgb, grad_depth, grad_alpha):
+        verts, faces, fidx, bary, tex, lit = ctx.saved_tensors
+        K, orig_size, S, ssaa, eps, fb, light = ctx.meta
+        B, N, _ = verts.shape
+        F, ts, C = tex.shape[1], tex.shape[2], tex.shape[5]
+        want_v, want_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        L = _lib.load()
+        st = _lib.stream()
+        Kc = (_lib.C.c_float * 9)(*K)
+        det = bool(L.g2s_get_deterministic())
+        dev = verts.device
+        gv = gt = None
+        # every scatter target must start at zero, as in the two Functions above: slices of the step's cleared
+        # pool when there is one (acc_is_zero = 1), else the call clears them itself
+        if want_v and grad_depth is not None:
+            g = grad_depth.contiguous().float()
+            ws, ws_bytes = None, 0
+            if det:
+                ws_bytes = L.g2s_raster_bwd_workspace_bytes(B, N)
+                ws = _zp.take(((ws_bytes + 3) // 4,), dev)
+                pre = ws is not None
+                if ws is None:
+                    ws = _workspace(dev, ws_bytes)
+                gv = torch.empty_like(verts)
+            else:
+                gv = _zp.take(tuple(verts.shape), dev)
+                pre = gv is not None
+                if gv is None:
+                    gv = torch.empty_like(verts)
+            _lib.check(L.g2s_raster_depth_bwd_ex(_lib.ptr(verts), _lib.ptr(faces), _lib.ptr(g), _lib.ptr(fidx),
+                                                 _lib.ptr(bary), B, N, F, S, Kc, orig_size, ssaa, _lib.ptr(gv),
+                                                 _lib.ptr(ws), ws_bytes, int(pre), st))
+        if grad_rgb is not None and (want_v or want_t):
+            g = grad_rgb.contiguous().float()
+            # the light moves with the vertices only through its directional term
+            want_l = want_v and lit is not None and any(float(x) != 0.0 for x in light[1])
+            lshape = (B, F * (1 + fb), 3)
+            ws, ws_bytes, gc, gl = None, 0, None, None
+            if det:
+                ws_bytes = L.g2s_raster_rgba_bwd_workspace_bytes(B, N, F, ts, C, fb)
+                ws = _zp.take(((ws_bytes + 3) // 4,), dev)
+                pre = ws is not None
+                if ws is None:
+                    ws = _workspace(dev, ws_bytes)
+                gc = torch.empty_like(verts) if want_v else None
+                gt = torch.empty_like(tex) if want_t else None
+                gl = torch.empty(lshape, dtype=torch.float32, device=dev) if want_l else None
+            else:
+                gc = _zp.take(tuple(verts.shape), dev) if want_v else None
+                gt = _zp.take(tuple(tex.shape), dev) if want_t else None
+                gl = _zp.take(lshape, dev) if want_l else None
+                pre = (gc is not None or not want_v) and (gt is not None or not want_t) and (gl is not None or not want_l)
+                if not pre:     # one flag covers the three targets, as in RenderRgbFunction.backward
+                    gc = torch.empty_like(verts) if want_v else None
+                    gt = torch.empty_like(tex) if want_t else None
+                    gl = torch.empty(lshape, dtype=torch.float32, device=dev) if want_l else None
+            _lib.check(L.g2s_raster_rgba_bwd(_lib.ptr(verts), _lib.ptr(faces), _lib.ptr(fidx), _lib.ptr(bary),
+                                             _lib.ptr(tex), _lib.ptr(lit), _lib.ptr(g), B, N, F, S, Kc, orig_size,
+                                             ssaa, ts, C, fb, eps, _lib.ptr(gt), _lib.ptr(gc), _lib.ptr(gl),
+                                             _lib.ptr(ws), ws_bytes, int(pre), st))
+            if want_l:
+                # added to the texture path's camera-space gradient (acc_is_zero = 1: nothing is cleared); the
+                # fixed-point sums of deterministic mode need a cleared workspace of their own
+                ws, ws_bytes = None, 0
+                if det:
+                    ws_bytes = L.g2s_raster_bwd_workspace_bytes(B, N)
+                    ws = _zp.zeros(((ws_bytes + 3) // 4,), dev)
+                f3 = _lib.C.c_float * 3
+                _lib.check(L.g2s_face_light_bwd(_lib.ptr(verts), _lib.ptr(faces), _lib.ptr(gl), B, N, F, S, fb,
+                                                f3(*light[1]), f3(*light[2]), _lib.ptr(gc), _lib.ptr(ws),
+                                                ws_bytes, 1, st))
+            if want_v:
+                # the projection backward of either path runs in place over that path's own sums, so the two
+                # camera-space gradients meet here and not inside one accumulator
+                gv = gc if gv is None else gv.add_(gc)
+        return gv, gt, None, None, None, None, None, None, None, None, None, None, None
+
+
 class Renderer:
     """`nr.Renderer` for camera_mode='projection' (the only mode GAN2Shape uses)."""
 
@@ -205,6 +336,9 @@ class Renderer:
         self.near, self.far = near, far
         self.light_intensity_ambient = light_intensity_ambient
         self.light_intensity_directional = light_intensity_directional
+        self.light_color_ambient = light_color_ambient
+        self.light_color_directional = light_color_directional
+        self.light_direction = light_direction
         self.rasterizer_eps = 1e-3
         self._K_host = None
 
@@ -275,21 +409,29 @@ class Renderer:
             raise NotImplementedError("per-sample face lists are not supported: call per sample")
         return f0
 
-    def render_rgb(self, vertices, faces, textures, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
-        """[B, C, S, S] image of the textured mesh: rasterize with the constructor's near / far
-        (renderer.py:51), read each winning face's texture cube trilinearly at perspective-corrected
-        barycentric coordinates, background colour elsewhere, flip + 2x2 average.  Lighting: ambient
-        only (GAN2Shape builds the renderer with light_intensity_ambient=1, directional=0).
+    def _light(self):
+        """None while today's unlit path computes the same thing (no directional light, white ambient: the
+        ambient intensity is then a scale of the textures), else the host triple of g2s_face_light_fwd:
+        (intensity_ambient * color_ambient, intensity_directional * color_directional, direction)."""
+        ia, idr = float(self.light_intensity_ambient), float(self.light_intensity_directional)
+        ca = [float(v) for v in self.light_color_ambient]
+        cd = [float(v) for v in self.light_color_directional]
+        direction = [float(v) for v in self.light_direction]
+        if len(ca) != 3 or len(cd) != 3 or len(direction) != 3:
+            raise ValueError("light colours and light_direction have 3 components")
+        if idr == 0 and ca == [1.0, 1.0, 1.0]:
+            return None
+        return tuple(ia * v for v in ca), tuple(idr * v for v in cd), tuple(direction)
 
-        Differentiable w.r.t. `textures` and `vertices` (RenderRgbFunction): gradient of the texture
-        lookup, no silhouette term.  R, t and the ambient intensity are torch ops around the function,
-        so autograd carries them.  When neither input requires grad the result has no history."""
+    def _texture_args(self, vertices, faces, textures, K, R, t, dist_coeffs, orig_size):
+        """Argument checks and the positional arguments that RenderRgbFunction and RenderFunction share."""
         K = self.K if K is None else K
         R = self.R if R is None else R
         t = self.t if t is None else t
         orig_size = self.orig_size if orig_size is None else orig_size
-        if self.light_intensity_directional != 0:
-            raise NotImplementedError("directional lighting is not supported (GAN2Shape uses ambient light only)")
+        light = self._light()
+        if light is not None and textures.shape[-1] != 3:
+            raise ValueError(f"lighting needs 3 colour channels, got textures with C = {textures.shape[-1]}")
         if K is None:
             raise ValueError("camera_mode='projection' needs K")
         _lib.require_cuda(vertices, textures)
@@ -307,15 +449,80 @@ class Renderer:
         if tex.dim() != 6 or tex.shape[0] != B or tex.shape[1] != F or not (tex.shape[2] == tex.shape[3] == tex.shape[4]):
             raise ValueError(f"textures must be [B={B}, F={F}, T, T, T, C], got {tuple(tex.shape)}")
         C = tex.shape[5]
-        if self.light_intensity_ambient != 1:
+        if light is None and self.light_intensity_ambient != 1:
             tex = tex * float(self.light_intensity_ambient)
         bg = [float(v) for v in self.background_color][:C]
         bg += [bg[-1]] * (C - len(bg))
-        return RenderRgbFunction.apply(vertices, tex, f, self._host_K(K), orig_size, S, self.anti_aliasing,
-                                       self.fill_back, self.near, self.far, tuple(bg), self.rasterizer_eps)
+        return (vertices, tex, f, self._host_K(K), orig_size, S, self.anti_aliasing, self.fill_back, self.near,
+                self.far, tuple(bg), self.rasterizer_eps), light
 
-    def render(self, *a, **k):
-        raise NotImplementedError("render / render_silhouettes (alpha channel, silhouette gradients) are not part "
-                                  "of the boundary GAN2Shape uses (renderer.py:120,196)")
+    def _no_distortion(self, dist_coeffs):
+        dist_coeffs = self.dist_coeffs if dist_coeffs is None else dist_coeffs
+        if dist_coeffs is not None and bool((dist_coeffs != 0).any()):
+            raise NotImplementedError("lens distortion is not supported (GAN2Shape never sets it)")
 
-    render_silhouettes = render
+    def render_rgb(self, vertices, faces, textures, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
+        """[B, C, S, S] image of the textured mesh: rasterize with the constructor's near / far
+        (renderer.py:51), read each winning face's texture cube trilinearly at perspective-corrected
+        barycentric coordinates, background colour elsewhere, flip + 2x2 average.  Lighting: with
+        light_intensity_directional = 0 and a white ambient colour (GAN2Shape builds the renderer with
+        ambient 1, directional 0) the ambient intensity scales the textures; otherwise every face's colour
+        is multiplied by its light (g2s_face_light_fwd: ambient + directional, flat shading; C must be 3).
+
+        Differentiable w.r.t. `textures` and `vertices` (RenderRgbFunction; RenderFunction when lit):
+        gradient of the texture lookup and of the light, no silhouette term.  R, t and the unlit ambient
+        intensity are torch ops around the function, so autograd carries them.  When neither input
+        requires grad the result has no history."""
+        args, light = self._texture_args(vertices, faces, textures, K, R, t, dist_coeffs, orig_size)
+        if light is None:
+            return RenderRgbFunction.apply(*args)
+        return RenderFunction.apply(*args, light)[0]
+
+    def render(self, vertices, faces, textures, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
+        """(rgb [B, C, S, S], depth [B, S, S], alpha [B, S, S]) from ONE rasterization with the constructor's
+        near / far: rgb as render_rgb; depth as render_depth's kernel gives it with those near / far (background =
+        far); alpha = the share of a pixel's 2x2 samples that a face covers.  rgb and depth are differentiable
+        w.r.t. `vertices` (and rgb w.r.t. `textures`); ALPHA HAS NO GRADIENT: the package's silhouette-edge
+        heuristic is not rebuilt (nothing pins it)."""
+        self._no_distortion(dist_coeffs)
+        args, light = self._texture_args(vertices, faces, textures, K, R, t, dist_coeffs, orig_size)
+        return RenderFunction.apply(*args, light)
+
+    def render_silhouettes(self, vertices, faces, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
+        """alpha [B, S, S] of `render`, from one rasterization and no texture pass.  NO GRADIENT (see `render`)."""
+        K = self.K if K is None else K
+        R = self.R if R is None else R
+        t = self.t if t is None else t
+        orig_size = self.orig_size if orig_size is None else orig_size
+        self._no_distortion(dist_coeffs)
+        if K is None:
+            raise ValueError("camera_mode='projection' needs K")
+        _lib.require_cuda(vertices)
+        with torch.no_grad():
+            verts = vertices.float()
+            if self._needs_transform(R, t):
+                if R is not None:
+                    verts = torch.matmul(verts, R.reshape(-1, 3, 3).transpose(2, 1))
+                if t is not None:
+                    verts = verts + t.reshape(-1, 1, 3)
+            verts = verts.contiguous()
+            B, N, _ = verts.shape
+            S = self.image_size
+            f = self._shared_faces(faces, N, S)
+            F = 2 * (S - 1) * (S - 1) if f is None else f.shape[0]
+            ssaa = 2 if self.anti_aliasing else 1
+            L = _lib.load()
+            depth = torch.empty((B, S, S), dtype=torch.float32, device=verts.device)
+            fidx = torch.empty((B, S * ssaa, S * ssaa), dtype=torch.int32, device=verts.device)
+            bary = torch.empty((B, S * ssaa, S * ssaa, 3), dtype=torch.float32, device=verts.device)
+            ws = _workspace(verts.device, L.g2s_raster_workspace_bytes(B, N, F, S))
+            Kc = (_lib.C.c_float * 9)(*self._host_K(K))
+            _lib.check(L.g2s_raster_depth_fwd(_lib.ptr(verts), _lib.ptr(f), B, N, F, S, Kc, float(orig_size), ssaa,
+                                              int(bool(self.fill_back)), float(self.near), float(self.far),
+                                              _lib.ptr(depth), _lib.ptr(fidx), _lib.ptr(bary), _lib.ptr(ws),
+                                              ws.numel(), _lib.stream()))
+            alpha = torch.empty((B, S, S), dtype=torch.float32, device=verts.device)
+            _lib.check(L.g2s_raster_rgba_fwd(None, None, _lib.ptr(fidx), None, None, None, B, N, F, S, ssaa, 1, 1,
+                                             int(bool(self.fill_back)), None, 0.0, None, _lib.ptr(alpha),
+                                             _lib.stream()))
+        return alpha

@@ -61,7 +61,8 @@ int g2s_get_deterministic(void);
  * g2s_warp_verts_bwd / g2s_inv_warp_grid_bwd (gRt), g2s_smooth_loss_fwd (loss), g2s_shading_bwd (glight),
  * g2s_depth_head_bwd (gsum), g2s_grid_sample_bwd (gx, or the deterministic mode's fixed-point workspace),
  * g2s_raster_depth_bwd_ex (grad_verts, or its fixed-point workspace; g2s_raster_depth_bwd passes 0),
- * g2s_raster_rgb_bwd (grad_textures and grad_verts, or its fixed-point workspace). */
+ * g2s_raster_rgb_bwd (grad_textures and grad_verts, or its fixed-point workspace), g2s_raster_rgba_bwd (the same and
+ * grad_light), g2s_face_light_bwd (there it also means: add to what grad_verts holds). */
 
 /* ------------------------------------------------------------------------------------------
  * Differentiable depth rasterizer.
@@ -160,6 +161,62 @@ int g2s_raster_rgb_bwd(const float *verts, const int32_t *faces, const int32_t *
                        const float *K, float orig_size, int ssaa, int ts, int C, float eps,
                        float *grad_textures, float *grad_verts, void *workspace, size_t workspace_bytes,
                        int acc_is_zero, g2s_stream_t stream);
+
+/* Per-face light factor: replaces nr.lighting(faces, textures, intensity_ambient, intensity_directional,
+ * color_ambient, color_directional, direction) as nr.Renderer.render / render_rgb apply it (flat shading per
+ * face), evaluated on the camera-space vertices (after R, t, before projection).  PARITY UNPINNED, as recalled
+ * (SURVEY.md Appendix A), like the rasterizer entries.  For the face (v0, v1, v2):
+ *     n = cross(v0 - v1, v2 - v1) / max(|cross|, 1e-5),  light[c] = ambient[c] + directional[c] * max(0, dot(n, direction))
+ * and the reversed fill_back copy (v2, v1, v0) has the normal -n.
+ * verts, faces, B, n_verts, n_faces   as g2s_raster_depth_fwd (faces NULL: implicit regular grid of side S;
+ *                                     S is not read otherwise)
+ * ambient, directional, direction     HOST pointers, 3 floats each: intensity_ambient * color_ambient,
+ *                                     intensity_directional * color_directional, light direction (used as given)
+ * light_out  [B, n_faces * (1 + fill_back), 3], indexed like the ids in face_idx (reversed copies at f + n_faces) */
+int g2s_face_light_fwd(const float *verts, const int32_t *faces, int B, int n_verts, int n_faces, int S,
+                       int fill_back, const float *ambient, const float *directional, const float *direction,
+                       float *light_out, g2s_stream_t stream);
+
+/* Backward of the above w.r.t. verts (replaces the autograd of nr.lighting; PARITY UNPINNED, as recalled): through
+ * the max, the dot product, the normalisation (no gradient while its 1e-5 clamp is active) and the cross product.
+ * grad_light [B, n_faces * (1 + fill_back), 3].  The gradient is ADDED to grad_verts [B, n_verts, 3] (camera xyz):
+ *   acc_is_zero = 0  the call clears what it adds into first: grad_verts ends as the light's gradient alone.
+ *   acc_is_zero = 1  no memset: grad_verts holds zeros or a camera-space gradient this one joins (Renderer.render adds
+ *                    it to the texture pass's), and in deterministic mode the workspace is already zero.
+ * Float atomics; in deterministic mode (g2s_set_deterministic) the sums are 2^-40 fixed point in `workspace`
+ * (>= g2s_raster_bwd_workspace_bytes(B, n_verts) bytes, as g2s_raster_depth_bwd_ex; NULL / short:
+ * G2S_ERR_WORKSPACE) and reach grad_verts in one rounding per element: bit-identical from run to run. */
+int g2s_face_light_bwd(const float *verts, const int32_t *faces, const float *grad_light, int B, int n_verts,
+                       int n_faces, int S, int fill_back, const float *directional, const float *direction,
+                       float *grad_verts, void *workspace, size_t workspace_bytes, int acc_is_zero,
+                       g2s_stream_t stream);
+
+/* Texture pass with light and alpha: the superset of g2s_raster_rgb_fwd that nr.Renderer.render needs (rgb and
+ * alpha of one rasterization; PARITY UNPINNED, as recalled).  Arguments as g2s_raster_rgb_fwd, plus
+ * light      NULL, or [B, n_faces * (1 + fill_back), 3] (g2s_face_light_fwd; C must be 3): the sample's colour is
+ *            multiplied channel-wise by light[b, winner] before background selection; background samples stay unlit.
+ * fill_back  what g2s_raster_depth_fwd was given for these maps (read only with light)
+ * alpha_out  NULL, or [B, S, S]: the share of the pixel's ssaa^2 samples that have a winner, flipped and averaged
+ *            like rgb.
+ * textures, light and rgb_out all NULL: alpha alone (nr.Renderer.render_silhouettes), no texture is read; only
+ * face_idx, B, S, ssaa and alpha_out are used. */
+int g2s_raster_rgba_fwd(const float *verts, const int32_t *faces, const int32_t *face_idx, const float *bary,
+                        const float *textures, const float *light, int B, int n_verts, int n_faces, int S,
+                        int ssaa, int ts, int C, int fill_back, const float *background, float eps,
+                        float *rgb_out, float *alpha_out, g2s_stream_t stream);
+
+/* Backward of the above (alpha has no gradient: NO SILHOUETTE TERM, as g2s_raster_rgb_bwd).  grad_textures and
+ * grad_verts as g2s_raster_rgb_bwd with the incoming colour gradient scaled by the light;
+ * grad_light [B, n_faces * (1 + fill_back), 3] (NULL: not computed; needs light) is the sum over the face's samples
+ * of grad_colour * unlit colour — feed it to g2s_face_light_bwd.  acc_is_zero and the deterministic mode's fixed-point
+ * workspace (>= g2s_raster_rgba_bwd_workspace_bytes bytes) cover all three gradients.  light = grad_light = NULL is
+ * g2s_raster_rgb_bwd, bit for bit. */
+size_t g2s_raster_rgba_bwd_workspace_bytes(int B, int n_verts, int n_faces, int ts, int C, int fill_back);
+int g2s_raster_rgba_bwd(const float *verts, const int32_t *faces, const int32_t *face_idx, const float *bary,
+                        const float *textures, const float *light, const float *grad_rgb, int B, int n_verts,
+                        int n_faces, int S, const float *K, float orig_size, int ssaa, int ts, int C, int fill_back,
+                        float eps, float *grad_textures, float *grad_verts, float *grad_light, void *workspace,
+                        size_t workspace_bytes, int acc_is_zero, g2s_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * fused bias + activation.
