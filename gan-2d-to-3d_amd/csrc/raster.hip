@@ -566,6 +566,8 @@ extern "C" int g2s_raster_tune(int waves_per_tile) {
     return G2S_OK;
 }
 
+extern "C" int g2s_raster_get_tune(void) { return g_force_waves; }
+
 extern "C" int g2s_raster_depth_fwd(const float *verts, const int32_t *faces, int B, int n_verts,
                                     int n_faces, int S, const float *K, float orig_size, int ssaa,
                                     int fill_back, float near_, float far_, float *depth_out,

@@ -31,6 +31,7 @@ SIGNATURES = {
     "g2s_get_deterministic": (_i, []),
     "g2s_raster_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "g2s_raster_tune": (_i, [_i]),
+    "g2s_raster_get_tune": (_i, []),
     "g2s_raster_depth_fwd": (_i, [_p, _p, _i, _i, _i, _i, _p, _f, _i, _i, _f, _f, _p, _p, _p, _p, _sz, _p]),
     "g2s_raster_depth_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _f, _i, _p, _p]),
     "g2s_raster_bwd_workspace_bytes": (_sz, [_i, _i]),

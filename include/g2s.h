@@ -97,8 +97,10 @@ int g2s_raster_depth_fwd(const float *verts, const int32_t *faces, int B, int n_
 
 /* Tuning hook (tools/bench_raster.py): waves_per_tile = 4 runs the 4 waves of a workgroup on ONE
  * 8x8-sample tile, 1 gives every wave its own tile, 0 restores the built-in choice (4 when
- * B * tiles <= 4096).  Calling thread only; outputs are bit-identical either way. */
+ * B * tiles <= 4096).  Calling thread only; outputs are bit-identical either way.  Any other value is
+ * G2S_ERR_INVALID and leaves the setting as it was; g2s_raster_get_tune returns the current one. */
 int g2s_raster_tune(int waves_per_tile);
+int g2s_raster_get_tune(void);
 
 /* Backward of the above w.r.t. verts (neural_renderer backward_depth_map + vertices_to_faces +
  * projection backward).
