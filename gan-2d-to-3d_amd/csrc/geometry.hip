@@ -196,6 +196,9 @@ __global__ __launch_bounds__(256) void inv_warp_grid_bwd(const float *__restrict
 // ------------------------------------------------------------------ smoothness loss
 // loss = mean|dx2| + mean|dxdy| + mean|dydx| + mean|dy2| over a [N, H, W] map (losses.py:54-79);
 // dxdy == dydx element-wise (mixed second difference).  grid (ceil(W/32), ceil(H/8), N), block (32, 8)
+// Where it differs from the reference by definition: a term whose extent is empty (dx2 for W <= 2, dy2 for
+// H <= 2, the mixed terms for H or W = 1) contributes 0 (smooth_weights); the reference's mean() of an
+// empty tensor is NaN.
 __device__ __forceinline__ float sgn(float v) { return (v > 0.0f) ? 1.0f : ((v < 0.0f) ? -1.0f : 0.0f); }
 
 __global__ __launch_bounds__(256) void smooth_loss_fwd(const float *__restrict__ pm, float *__restrict__ loss,

@@ -9,6 +9,10 @@
 // weighted squared difference); lanes run along pixels so every channel plane is read coalesced.
 // Backward gives the gradient w.r.t. f0 only (f1 is the target branch, no gradient in GAN2Shape:
 // model.py:159-160,275-276 mask the target with a detached mask of the input image).
+// Where it differs from the reference by definition: at a pixel whose f0 is zero in every channel the
+// gradient of the channel norm is taken as 0 (k2 = 0 below).  The reference's autograd gives NaN there
+// (the sqrt's infinite slope times 0).  The rest of the gradient at such a pixel, 2 w_c (u_c - v_c) / eps,
+// is kept; the trunk's ReLU gate (f0 > 0) removes it.
 #include "g2s_common.h"
 
 namespace g2s {
