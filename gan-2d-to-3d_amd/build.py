@@ -31,6 +31,7 @@ SOURCES = {
     "winograd4.hip": ["-fno-slp-vectorize"],
     "split_reduce.hip": [],
     "rowops.hip": [],
+    "projector.hip": [],
     "lpips.hip": [],
     "pool.hip": [],
     "losses.hip": [],

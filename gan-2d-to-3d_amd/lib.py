@@ -55,6 +55,11 @@ SIGNATURES = {
     "g2s_upfirdn2d_nba": (_i, [_p, _p, _p] + [_i] * 12 + [_p, _p, _p, _f, _f, _p]),
     "g2s_synth_bwd_rows": (_i, [_p] * 13 + [_i, _i, _i, _f, _f, _p]),
     "g2s_channel_sum": (_i, [_p, _p, _i, _i, _i, _p]),
+    "g2s_noise_grad": (_i, [_p, _p, _p, _i, _i, _i, _p]),
+    "g2s_noise_regularize_workspace_bytes": (_sz, [_p, _i, _i]),
+    "g2s_noise_regularize": (_i, [_p, _p, _p, _i, _i, _p, _p, _sz, _p]),
+    "g2s_noise_normalize_workspace_bytes": (_sz, [_p, _i, _i]),
+    "g2s_noise_normalize": (_i, [_p, _p, _i, _i, _p, _sz, _p]),
     "g2s_demod_fwd_multi": (_i, [_p, _p, _p, _p, _p, _i, _i, _f, _p]),
     "g2s_demod_bwd_multi": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
     "g2s_modconv_f16": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _p]),

@@ -366,6 +366,8 @@ class ModConvDemodFunction(Function):
 
 def modconv_demod(x, w, s, wsq, eps=1e-8, mode=PLAIN):
     """modconv(x, w, s, demodulation(s, wsq, eps), mode); one node when wsq is a constant."""
+    if not x.is_cuda:          # CPU tensors: plain torch (op/cpu_tensors.py's rule)
+        return modconv(x, w, s, torch.rsqrt(s.pow(2) @ wsq.t() + eps), mode)
     if wsq.requires_grad:
         return modconv(x, w, s, demodulation(s, wsq, eps), mode)
     _lib.require_cuda(s, wsq)
@@ -392,6 +394,9 @@ def _weight_grad(x, w, s, demod, gy, mode):
 
 def modconv(x, w, s=None, demod=None, mode=PLAIN):
     """x [B,Cin,H,W]; w [Cout,Cin,k,k] (scaled); s [B,Cin] or None; demod [B,Cout] or None."""
+    if not x.is_cuda:
+        from .op import cpu_tensors
+        return cpu_tensors.modconv(x, w, s, demod, mode)
     return ModConvFunction.apply(x, w, s, demod, mode)
 
 

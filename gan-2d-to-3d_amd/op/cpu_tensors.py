@@ -30,3 +30,17 @@ def upfirdn2d(x, kernel, up=1, down=1, pad=(0, 0)):
     out = F.conv2d(planes, taps)
     out = out[:, :, ::down, ::down]
     return out.reshape(n, c, out.shape[-2], out.shape[-1])
+
+
+def modconv(x, w, s=None, demod=None, mode=0):
+    """The modulated convolution in its input-scaling form (modconv.py): demod[b,o] * conv(s[b,c] * x[b,c], w[o,c]);
+    mode 0: stride 1, padding k // 2; 1: transposed, stride 2 (model.py:264-275 before its Blur); 2: stride 2, no padding."""
+    if s is not None:
+        x = x * s[:, :, None, None]
+    if mode == 0:
+        y = F.conv2d(x, w, padding=w.shape[2] // 2)
+    elif mode == 1:
+        y = F.conv_transpose2d(x, w.transpose(0, 1), stride=2)
+    else:
+        y = F.conv2d(x, w, stride=2)
+    return y if demod is None else y * demod[:, :, None, None]

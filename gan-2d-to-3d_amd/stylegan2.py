@@ -274,7 +274,10 @@ class StyledConv(nn.Module):
     def forward(self, input, style, noise=None):
         out = self.conv(input, style)
         frozen = not (self.noise.weight.requires_grad or self.activate.bias.requires_grad)
-        if noise is not None and noise.shape[0] == 1 and (frozen or not torch.is_grad_enabled()):
+        # the fused tail has no gradient for the map and no CPU form: a map that is being optimised (the projector's)
+        # and CPU tensors take the two modules below
+        fused = out.is_cuda and not (noise is not None and noise.requires_grad and torch.is_grad_enabled())
+        if fused and noise is not None and noise.shape[0] == 1 and (frozen or not torch.is_grad_enabled()):
             return fused_noise_bias_act(out, noise, self.noise.weight, self.activate.bias,
                                         self.activate.negative_slope, self.activate.scale)
         return self.activate(self.noise(out, noise=noise))

@@ -18,6 +18,10 @@ a full pass over the activation in HBM.  Here:
              output recovered from x: the leaky ReLU is invertible) — instead of rows_dot_scale twice, the
              accumulation of the two consumers' gradients, and the gate.
 
+The latent projector (projector.py) optimises the noise maps too: maps that require a gradient enter the node as
+tensor inputs and get noise_w * (sum over channels of the pre-activation gradient the row pass already writes), one
+launch of g2s_noise_grad per map; the forward, and every call with maps that require none, is unchanged.
+
 Same arithmetic as the op-by-op path up to fp32 summation order and the 1-ulp inversion of the activation
 in the demodulation gradient; tests/test_gpu_round4.py holds image and style gradients to that path."""
 import torch
@@ -92,11 +96,24 @@ def _tail(sc, noise):
     return (noise.contiguous(), sc.noise.weight.detach(), a.bias.detach(), a.negative_slope, a.scale)
 
 
+def _noise_grad(g_pre, layer):
+    """d loss / d noise map of a StyledConv from the gradient of its pre-activation (NoiseInjection, model.py:294-305:
+    pre = conv + weight * noise + bias with ONE map for the whole batch): weight * sum over channels — and samples."""
+    B, C, H, W = g_pre.shape
+    g = torch.empty((B, 1, H, W), dtype=torch.float32, device=g_pre.device)
+    _lib.check(_lib.load().g2s_noise_grad(_lib.ptr(g_pre), _lib.ptr(layer['tail'][1]), _lib.ptr(g), B, C, H * W, _lib.stream()))
+    return (g if B == 1 else g.sum(0, keepdim=True)).view(layer['noise_shape'])
+
+
 class _Synthesis(Function):
-    """image = synthesis(x0; s_0 .. s_{L-1}); gradients to the modulated styles only (frozen generator)."""
+    """image = synthesis(x0; s_0 .. s_{L-1}); gradients to the modulated styles (frozen generator) and — for the latent
+    projector — to the noise maps: `noise` is then None and the maps follow the styles as tensor inputs."""
 
     @staticmethod
     def forward(ctx, G, noise, x0, *styles):
+        ctx.noise_grads = noise is None
+        if noise is None:
+            styles, noise = styles[:-G.num_layers], styles[-G.num_layers:]
         styles = [s.contiguous() for s in styles]
         layers = []     # per StyledConv: dict(kind, sc, w, wsq, s, demod, x, yc, tail)
         rgbs = []       # per ToRGB: dict(tr, w, s, x)
@@ -123,7 +140,8 @@ class _Synthesis(Function):
             else:
                 yc = None
                 y = modconv_nba_raw(x, w, s, demod, tail[2], tail[0], tail[1], tail[3], tail[4])
-            layers.append(dict(up=up, sc=sc, w=w, wsq=wsq.contiguous(), s=s, demod=demod, x=x, yc=yc, y=y, tail=tail))
+            layers.append(dict(up=up, sc=sc, w=w, wsq=wsq.contiguous(), s=s, demod=demod, x=x, yc=yc, y=y, tail=tail,
+                               noise_shape=nz.shape))
             return y
 
         def to_rgb(tr, x, skip):
@@ -153,6 +171,10 @@ class _Synthesis(Function):
         nxt = None                       # (gxs, s, layer) of the up-sampling convolution above the current level
         order = []                       # (position in the style list, gradient)
         pending = []                     # (wsq, s, demod, gd, gs): the demodulation paths, added in ONE launch at the end
+        n_styles = 2 + 3 * (len(rgbs) - 1)
+        # the maps that ask for a gradient (layer index -> gradient); one launch each, none for the others
+        g_noise = {}
+        want = [ctx.noise_grads and ctx.needs_input_grad[3 + n_styles + i] for i in range(len(layers))]
         # positions in the style list: conv1 0, to_rgb1 1, then (up, plain, rgb) triples
         li, ri = len(layers) - 1, len(rgbs) - 1
         while ri >= 0:
@@ -169,6 +191,8 @@ class _Synthesis(Function):
                 order.append((nxt[3], dot_U))
                 pending.append((U['wsq'], U['s'], U['demod'], U['gd'], dot_U))
             order.append((pos_T, dot_T))
+            if want[li]:
+                g_noise[li] = _noise_grad(g_pre, plain)
             if T['up']:
                 tr = T['tr']
                 g_rgb = upfirdn2d_adjoint(g_rgb, tr.upsample.kernel, tr.upsample.factor, 1, tr.upsample.pad, T['hw'])
@@ -184,6 +208,8 @@ class _Synthesis(Function):
             g_pre_U, dot_P, _, _ = _rows(up['y'], gxs_P, plain['s'], None, None, up['tail'], None)
             order.append((pos_P, dot_P))
             pending.append((plain['wsq'], plain['s'], plain['demod'], gdot, dot_P))
+            if want[li - 1]:
+                g_noise[li - 1] = _noise_grad(g_pre_U, up)
             # the up-sampling layer: Blur's adjoint, demodulation gradient from the saved transposed-conv output
             blur = up['sc'].conv.blur
             g_yc = upfirdn2d_adjoint(g_pre_U, blur.kernel, 1, 1, blur.pad, tuple(up['yc'].shape[2:]))
@@ -197,13 +223,18 @@ class _Synthesis(Function):
         out = [None] * (max(p for p, _ in order) + 1)
         for p, g in order:
             out[p] = g
-        return (None, None, None) + tuple(out)
+        if not ctx.noise_grads:
+            return (None, None, None) + tuple(out)
+        return (None, None, None) + tuple(out) + tuple(g_noise.get(i) for i in range(len(want)))
 
 
 def eligible(G, x0, styles, noise):
-    """The one-node path serves the frozen generator on the fp32 kernels with fixed noise maps."""
+    """The one-node path serves the frozen generator on the fp32 kernels with ONE noise map per layer for the whole
+    batch (the epilogues read a single [H * W] map); per-sample maps [B > 1, 1, H, W] take the layer loop."""
     from . import modconv as mc
     if mc.OPERANDS != "f32" or not x0.is_cuda or x0.dtype != torch.float32 or any(nz is None for nz in noise):
+        return False
+    if any(nz.shape[0] != 1 for nz in noise):
         return False
     if any(p.requires_grad for p in G.parameters()):
         return False
@@ -211,4 +242,6 @@ def eligible(G, x0, styles, noise):
 
 
 def synthesize(G, noise, x0, styles):
+    if torch.is_grad_enabled() and any(nz.requires_grad for nz in noise):
+        return _Synthesis.apply(G, None, x0, *styles, *noise)     # differentiable inputs: the projector's noise maps
     return _Synthesis.apply(G, list(noise), x0, *styles)

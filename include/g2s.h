@@ -570,6 +570,39 @@ int g2s_synth_bwd_rows(const float *x, const float *g1, const float *s1, const f
                        g2s_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The latent projector's additions to the frozen generator (csrc/projector.hip; stylegan2-pytorch/projector.py:16-44,
+ * gan-2d-to-3d_amd/projector.py).  No float atomics anywhere: every sum has one fixed order, and none depends on
+ * g2s_set_deterministic.
+ *
+ * g2s_noise_grad: the gradient of a StyledConv's noise map from the gradient of its pre-activation (the `out` of
+ *   g2s_synth_bwd_rows):  gnoise[b,i] = noise_w[0] * sum_c gpre[b,c,i].  gpre [B, C, n], gnoise [B, n] f32, noise_w a
+ *   device scalar.  16-byte loads when n % 4 == 0 and both pointers are 16-byte aligned, a scalar path otherwise.
+ *
+ * The two entries below take ALL noise maps of a generator in one call: HOST arrays of `maps` device pointers and
+ * sides (maps <= G2S_NOISE_MAX_MAPS; map m is [B, 1, side_m, side_m] f32, contiguous; every side a power of two,
+ * 4 .. 512; 1 <= B <= 64), scratch in a caller-provided workspace of at least *_workspace_bytes (0 for invalid
+ * arguments; contents undefined afterwards), no host synchronisation.  A NULL / short workspace is G2S_ERR_WORKSPACE;
+ * every check precedes the first launch.
+ *
+ * g2s_noise_regularize: value and gradient of the reference's noise_regularize.  Per map n_0, levels l = 0, 1, ...
+ *   of side S_l = S / 2^l; each adds mean(n_l * roll(n_l, 1, x))^2 + mean(n_l * roll(n_l, 1, y))^2, the means over all
+ *   B * S_l^2 elements and the rolls wrapping at S_l; the first level with S_l <= 8 is the last, otherwise n_{l+1} is
+ *   the 2x2 mean of n_l.  loss [1] (device) receives the sum over maps; grad (NULL: value only) is a HOST array of
+ *   device pointers, grad[m] shaped like map m and 16-byte aligned, and receives d loss / d n_0.  At most three
+ *   launches whatever the number of maps (two when no map has a side above 8).
+ * g2s_noise_normalize: n <- (n - mean) / std in place, mean and the unbiased (N - 1) standard deviation over all
+ *   elements of a map, batch included.  Two launches.
+ * ---------------------------------------------------------------------------------------- */
+#define G2S_NOISE_MAX_MAPS 32
+int g2s_noise_grad(const float *gpre, const float *noise_w, float *gnoise, int B, int C, int n, g2s_stream_t stream);
+size_t g2s_noise_regularize_workspace_bytes(const int *sides, int maps, int B);
+int g2s_noise_regularize(const void *const *noise, const void *const *grad, const int *sides, int maps, int B,
+                         float *loss, void *workspace, size_t workspace_bytes, g2s_stream_t stream);
+size_t g2s_noise_normalize_workspace_bytes(const int *sides, int maps, int B);
+int g2s_noise_normalize(const void *const *noise, const int *sides, int maps, int B, void *workspace,
+                        size_t workspace_bytes, g2s_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * LPIPS per-layer tail (csrc/lpips.hip): unit-normalise both feature maps over channels, weighted
  * squared difference, spatial mean — lpips/networks_basic.py:64-92 + lpips/__init__.py:40-42.
  * f0, f1 [N, C, HW] f32; w [C] (the 1x1 `lin` weights); out [N] is ACCUMULATED into
