@@ -38,6 +38,7 @@ SOURCES = {
     "geometry.hip": ["-ffp-contract=off"],
     "grid_sample.hip": ["-ffp-contract=off"],
     "priors.hip": ["-ffp-contract=off"],         # restates the torch expressions of priors.py operation by operation
+    "parsing.hip": [],
     "groupnorm.hip": [],
     "conv_wgrad.hip": [],
     "adam.hip": [],

@@ -110,6 +110,13 @@ SIGNATURES = {
     "g2s_prior_smooth": (_i, [_p, _i, _i, _i, _i, _d, _d, _p, _p, _sz, _p]),
     "g2s_prior_ellipsoid_workspace_bytes": (_sz, [_i]),
     "g2s_prior_ellipsoid": (_i, [_p, _i, _i, _d, _d, _d, _d, _p, _p, _sz, _p]),
+    "g2s_conv_stem7": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "g2s_maxpool3x3s2": (_i, [_p, _p, _i, _i, _i, _p]),
+    "g2s_adaptive_avgpool": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
+    "g2s_resize_bilinear": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "g2s_gate_add_act": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "g2s_parse_head_workspace_bytes": (_sz, [_i]),
+    "g2s_parse_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, C.c_uint32, _p, _p, _p, _p, _sz, _p]),
 }
 
 

@@ -509,6 +509,12 @@ class GAN2Shape(nn.Module):
                                                  clamp_border=False)
         return recon_im, recon_depth
 
+    def evaluate_results_masked(self, image, masking_model):
+        """evaluate_results with the depth masked as evaluate_results.py:103 does: NaN outside the object mask of
+        `masking_model` (parsing.MaskingModel)."""
+        recon_im, recon_depth = self.evaluate_results(image)
+        return recon_im, masking_model.image_mask(image, recon_depth)
+
     def reinitialize_model(self):
         """model.py:370-383 (never called by the reference's trainer)."""
         for name in GAN2Shape.NETS:

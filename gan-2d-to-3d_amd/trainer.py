@@ -40,10 +40,20 @@ class Trainer():
         self.save_ckpts = save_ckpts
         self.debug = debug
         self.capturable = capturable  # Adam(capturable=True): needed to record steps in HIP graphs
-        self.prior_generator = PriorGenerator(self.image_size, self.category,
-                                              model_config.get('prior_name', 'ellipsoid'),
+        prior_name = model_config.get('prior_name', 'ellipsoid')
+        mask_accepts_batch = False
+        if masking_model is None and model_config.get('parsing_ckpt_dir'):
+            # config `parsing_ckpt_dir` names an existing directory: the parsing net of the category (parsing.py)
+            # supplies the masks, batched; otherwise the synthetic mask stays
+            from .parsing import masking_model_from_config
+            parser = masking_model_from_config(model_config, device=self.device)
+            if parser is not None:
+                masking_model = parser.confidence_mask if 'confidence' in prior_name else parser.image_mask
+                mask_accepts_batch = True
+        self.prior_generator = PriorGenerator(self.image_size, self.category, prior_name,
                                               masking_model=masking_model,
-                                              on_device=model_config.get('prior_on_device', False))
+                                              on_device=model_config.get('prior_on_device', False),
+                                              mask_accepts_batch=mask_accepts_batch)
         self.optim_step1 = Trainer.default_optimizer([self.model.albedo_net], lr=self.learning_rate,
                                                      capturable=capturable)
         self.optim_step2 = Trainer.default_optimizer([self.model.offset_encoder_net],

@@ -753,6 +753,51 @@ size_t g2s_prior_ellipsoid_workspace_bytes(int B);
 int g2s_prior_ellipsoid(const float *mask, int B, int S, double threshold, double radius, double near,
                         double far, float *out, void *workspace, size_t workspace_bytes, g2s_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Parsing networks behind the object masks (csrc/parsing.hip): what BiSeNet / PSPNet (GAN2Shape/networks.py:247-586,
+ * resnet.py) and MaskingModel (GAN2Shape/model.py:473-551) need beside g2s_conv2d.  All tensors f32, contiguous
+ * NCHW; `planes` = B * C.  No float atomics: results are bit-reproducible from run to run.  Nothing
+ * synchronises; every check precedes the first launch; an empty batch (B or planes = 0) returns G2S_OK.
+ * The ABI version stays 1, as for every earlier addition: symbols are only added.
+ *
+ *   g2s_conv_stem7        y = act(conv(x, w) + bias), w [M, 3, 7, 7], stride 2, padding 3, x [B, 3, H, W],
+ *                         y [B, M, (H-1)/2+1, (W-1)/2+1]; bias [M] or NULL; relu != 0: ReLU.  (g2s_conv2d stops at k = 5.)
+ *   g2s_maxpool3x3s2      3x3 window, stride 2, padding 1 that behaves as -inf; y [planes, (H-1)/2+1, (W-1)/2+1].
+ *   g2s_adaptive_avgpool  y[i, j] = mean of x[floor(i H / out_h) .. ceil((i+1) H / out_h), same in W): PyTorch's
+ *                         adaptive_avg_pool2d, also its 'area' interpolation; out_h > H is allowed.
+ *   g2s_resize_bilinear   PyTorch's bilinear interpolation with or without align_corners.
+ *   g2s_gate_add_act      y = act(x * s' + t + r): x, r, y [planes, HW]; s, t [planes]; each of s, t, r may be NULL.
+ *                         s' = s, through a logistic sigmoid if sigmoid != 0, plus 1 if plus_one != 0 (both need s);
+ *                         act = ReLU if relu != 0.  y must not overlap x or r.
+ *   g2s_parse_head        logits [B, C, h, w], C <= 32.  For every pixel of the size x size grid the C logits are
+ *                         interpolated bilinearly (align_corners = 1) and reduced by a rule given as data:
+ *                           mode 0 (hard mask):  v = 1 if the argmax over the channels other than `drop` (-1: none;
+ *                                                ties to the lowest channel) is a member of class_set (bit c = channel
+ *                                                c of the logits), else 0;
+ *                           mode 1 (confidence): v = sum of the channels in class_set (drop must be -1).
+ *                         out [B, 1, S, S], S <= size, receives the area average of v over the adaptive bins
+ *                         (g2s_adaptive_avgpool's); the full-resolution logits are never stored.  Then, per sample:
+ *                         mode 0: a sample without a single member pixel gets out = 1 everywhere (and full_mask = 1);
+ *                         fallback[b] = 1 for such a sample, else 0.  mode 1: out = (out - min v) / (max v - min v)
+ *                         with the full-resolution min and max (the affine map commutes with the average);
+ *                         fallback[b] = 0.  full_mask (mode 0 only, may be NULL): uint8 [B, 1, size, size], v per
+ *                         pixel.  fallback may be NULL.  workspace: >= g2s_parse_head_workspace_bytes(B) bytes,
+ *                         scratch of one call (cleared by the call); NULL / short is G2S_ERR_WORKSPACE.
+ * ---------------------------------------------------------------------------------------- */
+int g2s_conv_stem7(const float *x, const float *w, const float *bias, float *y, int B, int M, int H, int W, int relu,
+                   g2s_stream_t stream);
+int g2s_maxpool3x3s2(const float *x, float *y, int planes, int H, int W, g2s_stream_t stream);
+int g2s_adaptive_avgpool(const float *x, float *y, int planes, int H, int W, int out_h, int out_w,
+                         g2s_stream_t stream);
+int g2s_resize_bilinear(const float *x, float *y, int planes, int H, int W, int out_h, int out_w, int align_corners,
+                        g2s_stream_t stream);
+int g2s_gate_add_act(const float *x, const float *s, const float *t, const float *r, float *y, int planes, int HW,
+                     int sigmoid, int plus_one, int relu, g2s_stream_t stream);
+size_t g2s_parse_head_workspace_bytes(int B);
+int g2s_parse_head(const float *logits, int B, int C, int h, int w, int size, int S, int mode, int drop,
+                   uint32_t class_set, float *out, uint8_t *full_mask, int *fallback, void *workspace,
+                   size_t workspace_bytes, g2s_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
