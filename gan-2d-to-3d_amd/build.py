@@ -38,6 +38,7 @@ SOURCES = {
     "geometry.hip": ["-ffp-contract=off"],
     "grid_sample.hip": ["-ffp-contract=off"],
     "priors.hip": ["-ffp-contract=off"],         # restates the torch expressions of priors.py operation by operation
+    "metrics.hip": ["-ffp-contract=off"],        # as geometry.hip (shared normals); var = E[d^2] - E[d]^2 is exactly 0 for one pixel
     "parsing.hip": [],
     "groupnorm.hip": [],
     "conv_wgrad.hip": [],

@@ -11,6 +11,7 @@
 // workgroup and added with one float atomic per workgroup and component.
 #include <algorithm>
 #include "g2s_common.h"
+#include "normal_core.h"
 
 namespace g2s {
 
@@ -247,18 +248,7 @@ __global__ __launch_bounds__(256) void smooth_loss_bwd(const float *__restrict__
 // ------------------------------------------------------------------ normals from depth
 // renderer.py:127-139: g = d * ray; n = (g[y,x+1] - g[y,x-1]) x (g[y+1,x] - g[y-1,x]) in the interior,
 // (0,0,1) on the border; normal = n / (|n| + 1e-7).  grid (ceil(W/32), ceil(H/8), B), block (32, 8)
-constexpr float NORMAL_EPS = 1e-7f;
-
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 cross3(V3 a, V3 b) { return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ V3 sub3(V3 a, V3 b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-
-__device__ __forceinline__ V3 pt3(const float *d, const float *rays, int W, int y, int x) {
-    const float dd = d[y * W + x];
-    const float *r = rays + 3 * (y * W + x);
-    return V3{r[0] * dd, r[1] * dd, r[2] * dd};
-}
-
+// (V3, cross3, sub3, pt3 and NORMAL_EPS: normal_core.h, shared with metrics.hip)
 __global__ __launch_bounds__(256) void normal_fwd(const float *__restrict__ depth,
                                                   const float *__restrict__ rays,
                                                   float *__restrict__ normal, int H, int W) {

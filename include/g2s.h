@@ -798,6 +798,36 @@ int g2s_parse_head(const float *logits, int B, int C, int h, int w, int size, in
                    uint32_t class_set, float *out, uint8_t *full_mask, int *fallback, void *workspace,
                    size_t workspace_bytes, g2s_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Depth and normal accuracy of a recovered depth against a ground-truth depth (csrc/metrics.hip): the
+ * figures of the BFM table of the GAN2Shape / Unsup3D papers, per image, in two launches.
+ * depth_pred, depth_gt, mask_pred, mask_gt [B, H, W] f32 (either mask may be NULL: all ones); rays [H * W, 3],
+ * K^-1 (u, v, 1) per pixel; out [B, 5] = {count, mae, mse, side, mad_deg} of image b.
+ *   raw validity   mask_pred > 0.5 (or NULL), mask_gt > 0.5 (or NULL), both depths finite and > 0.  A NaN
+ *                  depth is "outside the object", not an error.
+ *   erode != 0     a pixel counts if it and its eight neighbours are raw-valid; outside the image is invalid, so
+ *                  the border row and column drop out (avg_pool2d(mask, 3, 1, 1) > 0.99 of the papers' evaluation).
+ *   erode == 0     raw validity decides.  A pixel on the border, or one of whose four stencil neighbours has a
+ *                  non-finite depth (in either map), counts for count, mae, mse, side but not for mad_deg;
+ *                  mad_deg divides by its own count.
+ *   count          number n of counted pixels (exact to 2^24);  mae = sum |p - g| / n;  mse = sum (p - g)^2 / n
+ *   side           delta = log p - log g;  sqrt(max(0, sum (delta - mean delta)^2 / n)), moments held in double
+ *   mad_deg        mean angle, in degrees, between the normals n_p and n_g of the two depths, each computed as
+ *                  g2s_normal_fwd does for interior pixels (P = rays * depth; cross(P(y, x+1) - P(y, x-1),
+ *                  P(y+1, x) - P(y-1, x)) / (norm + 1e-7)).  The angle is atan2(|n_p x n_g|, n_p . n_g): it
+ *                  equals acos(n_p . n_g) for unit vectors and does not depend on the 1e-7 that leaves them
+ *                  slightly shorter than 1.
+ *   n == 0         count 0, the four metrics NaN; no pixel with a stencil: mad_deg NaN.
+ * 3 <= H, W <= 32768, 1 <= B <= 65535.  workspace: >= g2s_depth_metrics_workspace_bytes(B, H, W) bytes, 8-byte
+ * aligned, scratch of one call; NULL / short is G2S_ERR_WORKSPACE.  Every check precedes the first launch;
+ * nothing allocates or synchronises; no atomics: every sum has one fixed order, the output is bit-identical
+ * from run to run.
+ * ---------------------------------------------------------------------------------------- */
+size_t g2s_depth_metrics_workspace_bytes(int B, int H, int W);
+int g2s_depth_metrics(const float *depth_pred, const float *depth_gt, const float *mask_pred, const float *mask_gt,
+                      const float *rays, int B, int H, int W, int erode, float *out, void *workspace,
+                      size_t workspace_bytes, g2s_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
