@@ -20,6 +20,7 @@ SOURCES = {
     "api.hip": [],
     "raster.hip": ["-ffp-contract=off"],  # bit-parity with the oracle's unfused arithmetic
     "raster_rgb.hip": ["-ffp-contract=off"],
+    "sweep.hip": ["-ffp-contract=off"],          # the unfused order its torch statement (sweep_shade_torch) has
     "face_light.hip": ["-ffp-contract=off"],     # forward and backward agree on the sign of dot(n, direction)
     "fused_bias_act.hip": [],
     "upfirdn2d.hip": [],

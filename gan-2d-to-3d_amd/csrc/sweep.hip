@@ -1,0 +1,252 @@
+// sweep.hip — the viewing path: V poses of the same depth mesh per image in three launches (Renderer.render_sweep):
+// g2s_sweep_verts, g2s_raster_depth_fwd over the B*V posed meshes, g2s_sweep_shade.  The loop it stands beside
+// (Renderer._sweep) rebuilds the texture cubes of the whole image and runs its own rotate / rasterise / texture
+// pass per pose; here the image and the normals are read in place as per-vertex attributes that all V frames of
+// an image share, and the shading of GAN2Shape/model.py:355-358 (get_shading) is applied in the same pass.
+//
+//   sweep_verts_kernel<W>   out[b*V + v, n] = A[b,v] . verts[b,n] + t[b,v].  A streaming write of B*V*N*3 floats.
+//                           A thread owns W consecutive floats of the flat [N*3] row (W = 4: one 16-byte store per
+//                           frame; W = 1 when N*3 is no multiple of 4).  The two (one) vertices those floats belong
+//                           to are loaded ONCE into registers and reused for the SWEEP_VPB frames of the block; the
+//                           twelve pose values of a frame are wave-uniform loads.  Grid (floats / W / 256, V /
+//                           SWEEP_VPB, B): the frames of an image are spread over the grid so that B = 1 fills the
+//                           device too, the re-read of the vertices by the other frame groups hits L2.
+//   sweep_shade_kernel      one thread per output pixel, as raster_rgb_kernel: per supersample the winner's three
+//                           vertices, perspective-correct weights u_k = w_k D / z_k (D = 1 / sum w_k / z_k, z of the
+//                           POSED vertices; no clamp, no renormalisation), attribute and normal gathered at the
+//                           vertices from the maps of image b = f / V (a few hundred KB, resident in L2 for all V
+//                           frames), then the mode's colour; flip + ssaa x ssaa average and alpha as
+//                           g2s_raster_rgba_fwd.  No atomics: bit-identical from run to run.
+// No backward: nothing here carries a gradient.
+#include "g2s_common.h"
+#include "raster_core.h"
+
+namespace g2s {
+
+constexpr int SWEEP_VPB = 8;   // frames per workgroup of sweep_verts_kernel
+
+template <int W>
+__global__ __launch_bounds__(256) void sweep_verts_kernel(const float *__restrict__ verts,
+                                                          const float *__restrict__ pose, float *__restrict__ out,
+                                                          int V, long row) {   // row = N * 3 floats
+    const long j0 = ((long)blockIdx.x * 256 + threadIdx.x) * W;
+    if (j0 >= row) return;
+    const int b = blockIdx.z;
+    const long n0 = j0 / 3;
+    constexpr int NV = W == 1 ? 1 : 2;            // vertices that W consecutive floats touch (W <= 4)
+    const long nlast = (j0 + W - 1) / 3;
+    float p[NV][3];
+    const float *src = verts + (size_t)b * row;
+#pragma unroll
+    for (int i = 0; i < NV; i++) {
+        const long n = n0 + i <= nlast ? n0 + i : nlast;
+#pragma unroll
+        for (int k = 0; k < 3; k++) p[i][k] = src[n * 3 + k];
+    }
+    int which[W], comp[W];
+#pragma unroll
+    for (int i = 0; i < W; i++) {
+        const long n = (j0 + i) / 3;
+        which[i] = (int)(n - n0);
+        comp[i] = (int)(j0 + i - n * 3);
+    }
+    const int v0 = blockIdx.y * SWEEP_VPB, v1 = min(V, v0 + SWEEP_VPB);
+    for (int v = v0; v < v1; v++) {
+        const float *q = pose + ((size_t)b * V + v) * 12;     // wave-uniform
+        float o[W];
+#pragma unroll
+        for (int i = 0; i < W; i++) {
+            const float x = which[i] ? p[NV - 1][0] : p[0][0];
+            const float y = which[i] ? p[NV - 1][1] : p[0][1];
+            const float z = which[i] ? p[NV - 1][2] : p[0][2];
+            const int c = comp[i];
+            const float a0 = c == 0 ? q[0] : c == 1 ? q[3] : q[6];
+            const float a1 = c == 0 ? q[1] : c == 1 ? q[4] : q[7];
+            const float a2 = c == 0 ? q[2] : c == 1 ? q[5] : q[8];
+            const float t = c == 0 ? q[9] : c == 1 ? q[10] : q[11];
+            o[i] = ((a0 * x + a1 * y) + a2 * z) + t;
+        }
+        float *dst = out + ((size_t)b * V + v) * row + j0;
+        if (W == 4) {
+            *reinterpret_cast<float4 *>(dst) = make_float4(o[0], o[W > 1 ? 1 : 0], o[W > 2 ? 2 : 0], o[W > 3 ? 3 : 0]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < W; i++) dst[i] = o[i];
+        }
+    }
+}
+
+struct ShadeParams {
+    const float *verts;      // [B*V, N, 3] posed
+    const int32_t *faces;    // [F, 3] or NULL (implicit regular grid)
+    const int32_t *face_idx; // [B*V, is, is]
+    const float *bary;       // [B*V, is, is, 3]
+    const float *attr;       // [B, C, N] or NULL
+    const float *normal;     // [B, N, 3] or NULL
+    const float *pose;       // [B, V, 12] or NULL
+    const float *light;      // [B*V, 5] or NULL
+    float *out;              // [B*V, Cout, S, S]
+    float *alpha;            // [B*V, S, S] or NULL
+    int B, V, N, F, S, is, ssaa, C, Cout, fill_back;
+    float grey;
+    float bg[4];
+};
+
+// Colour of one supersample of frame f.  Returns whether the sample has a winner.
+template <bool IMPLICIT, int MODE>
+__device__ __forceinline__ bool shade_sample(const ShadeParams &p, int f, int b, int yi, int xi, float col[4]) {
+    const size_t si = ((size_t)f * p.is + yi) * p.is + xi;
+    const int fn = p.face_idx[si];
+    if (fn < 0) {
+        for (int c = 0; c < p.Cout; c++) col[c] = p.bg[c];
+        return false;
+    }
+    const int g = fn % p.F;
+    const bool rev = p.fill_back && fn >= p.F;
+    int v[3];
+    if (IMPLICIT) {
+        implicit_face(g, p.S, v);
+    } else {
+        v[0] = p.faces[3 * g];
+        v[1] = p.faces[3 * g + 1];
+        v[2] = p.faces[3 * g + 2];
+    }
+    if (rev) {
+        const int t = v[0];
+        v[0] = v[2];
+        v[2] = t;
+    }
+    float w[3], z[3], u[3];
+    for (int k = 0; k < 3; k++) {
+        w[k] = p.bary[3 * si + k];
+        z[k] = p.verts[((size_t)f * p.N + v[k]) * 3 + 2];
+    }
+    const float depth = 1.0f / (w[0] / z[0] + w[1] / z[1] + w[2] / z[2]);
+    for (int k = 0; k < 3; k++) u[k] = w[k] * depth / z[k];
+    float a[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (MODE == 0 || MODE == 1) {
+        for (int c = 0; c < p.C; c++) {
+            const float *src = p.attr + ((size_t)b * p.C + c) * p.N;
+            a[c] = (u[0] * src[v[0]] + u[1] * src[v[1]]) + u[2] * src[v[2]];
+        }
+    }
+    if (MODE == 0) {
+        for (int c = 0; c < p.C; c++) col[c] = a[c];
+        return true;
+    }
+    const float *nm = p.normal + (size_t)b * p.N * 3;
+    float m[3], n[3];
+    for (int c = 0; c < 3; c++)
+        m[c] = (u[0] * nm[(size_t)v[0] * 3 + c] + u[1] * nm[(size_t)v[1] * 3 + c]) + u[2] * nm[(size_t)v[2] * 3 + c];
+    const float *A = p.pose + ((size_t)f) * 12;   // f = b*V + v indexes [B, V, 12] directly
+    for (int c = 0; c < 3; c++) n[c] = (A[3 * c] * m[0] + A[3 * c + 1] * m[1]) + A[3 * c + 2] * m[2];
+    const float len = sqrtf((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+    const float den = fmaxf(len, 1e-12f);
+    for (int c = 0; c < 3; c++) n[c] = n[c] / den;
+    if (MODE == 3) {
+        for (int c = 0; c < 3; c++) col[c] = n[c];
+        return true;
+    }
+    const float *l = p.light + (size_t)f * 5;
+    const float dot = (n[0] * l[2] + n[1] * l[3]) + n[2] * l[4];
+    const float shade = l[0] + l[1] * fmaxf(dot, 0.0f);
+    if (MODE == 1) {
+        for (int c = 0; c < p.C; c++) col[c] = (a[c] / 2.0f + 0.5f) * shade * 2.0f - 1.0f;
+    } else {
+        const float s = p.grey * shade * 2.0f - 1.0f;
+        for (int c = 0; c < 3; c++) col[c] = s;
+    }
+    return true;
+}
+
+template <bool IMPLICIT, int MODE>
+__global__ __launch_bounds__(256) void sweep_shade_kernel(ShadeParams p) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)p.B * p.V * p.S * p.S) return;
+    const int f = (int)(i / ((long)p.S * p.S));
+    const int b = f / p.V;
+    const int r = (int)((i / p.S) % p.S), c0 = (int)(i % p.S);
+    float sum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    int covered = 0;
+    for (int dy = 0; dy < p.ssaa; dy++)
+        for (int dx = 0; dx < p.ssaa; dx++) {
+            const int yi = p.is - 1 - (r * p.ssaa + dy);   // row of the (unflipped) raster
+            float col[4];
+            if (shade_sample<IMPLICIT, MODE>(p, f, b, yi, c0 * p.ssaa + dx, col)) covered++;
+            for (int c = 0; c < p.Cout; c++) sum[c] += col[c];
+        }
+    const float inv = 1.0f / (float)(p.ssaa * p.ssaa);
+    for (int c = 0; c < p.Cout; c++) p.out[(((size_t)f * p.Cout + c) * p.S + r) * p.S + c0] = sum[c] * inv;
+    if (p.alpha) p.alpha[((size_t)f * p.S + r) * p.S + c0] = (float)covered * inv;
+}
+
+template <bool IMPLICIT>
+static void launch_shade(const ShadeParams &p, int mode, hipStream_t st) {
+    const int blocks = cdiv((long)p.B * p.V * p.S * p.S, 256);
+    if (mode == 0) sweep_shade_kernel<IMPLICIT, 0><<<blocks, 256, 0, st>>>(p);
+    else if (mode == 1) sweep_shade_kernel<IMPLICIT, 1><<<blocks, 256, 0, st>>>(p);
+    else if (mode == 2) sweep_shade_kernel<IMPLICIT, 2><<<blocks, 256, 0, st>>>(p);
+    else sweep_shade_kernel<IMPLICIT, 3><<<blocks, 256, 0, st>>>(p);
+}
+
+}  // namespace g2s
+
+using namespace g2s;
+
+extern "C" int g2s_sweep_verts(const float *verts, const float *pose, float *out, int B, int V, int n_verts,
+                               g2s_stream_t stream) {
+    G2S_REQUIRE(verts && pose && out, "g2s_sweep_verts: NULL pointer argument");
+    G2S_REQUIRE(B > 0 && V > 0 && n_verts > 0, "g2s_sweep_verts: sizes must be positive");
+    G2S_REQUIRE(B <= 65535 && V <= 65535 * SWEEP_VPB, "g2s_sweep_verts: B = %d, V = %d exceed the grid", B, V);
+    const long row = (long)n_verts * 3;
+    const bool wide = row % 4 == 0 && ((uintptr_t)out & 15) == 0;
+    const dim3 grid(cdiv(wide ? row / 4 : row, 256), cdiv(V, SWEEP_VPB), B);
+    if (wide) sweep_verts_kernel<4><<<grid, 256, 0, as_stream(stream)>>>(verts, pose, out, V, row);
+    else sweep_verts_kernel<1><<<grid, 256, 0, as_stream(stream)>>>(verts, pose, out, V, row);
+    return check_launch("g2s_sweep_verts");
+}
+
+extern "C" int g2s_sweep_shade(const float *verts, const int32_t *faces, const int32_t *face_idx, const float *bary,
+                               const float *attr, const float *normal, const float *pose, const float *light, int B,
+                               int V, int n_verts, int n_faces, int S, int ssaa, int C, int fill_back, int mode,
+                               const float *background, float grey, float *rgb_out, float *alpha_out,
+                               g2s_stream_t stream) {
+    G2S_REQUIRE(mode >= 0 && mode <= 3, "g2s_sweep_shade: mode %d (0 texture, 1 shaded, 2 shape, 3 normal)", mode);
+    G2S_REQUIRE(verts && face_idx && bary && rgb_out && background, "g2s_sweep_shade: NULL pointer argument");
+    G2S_REQUIRE(B > 0 && V > 0 && n_verts > 0 && n_faces > 0 && S > 0, "g2s_sweep_shade: sizes must be positive");
+    G2S_REQUIRE((long)B * V <= 0x7fffffffL, "g2s_sweep_shade: B * V exceeds int");
+    G2S_REQUIRE(ssaa == 1 || ssaa == 2, "g2s_sweep_shade: ssaa must be 1 or 2");
+    G2S_REQUIRE(faces || (n_verts == S * S && n_faces == 2 * (S - 1) * (S - 1)),
+                "g2s_sweep_shade: implicit topology needs S*S vertices and 2(S-1)^2 faces");
+    const bool reads_attr = mode == 0 || mode == 1;
+    G2S_REQUIRE(!reads_attr || attr, "g2s_sweep_shade: mode %d reads attr, which is NULL", mode);
+    G2S_REQUIRE(!reads_attr || (C >= 1 && C <= 4), "g2s_sweep_shade: C = %d outside 1..4", C);
+    G2S_REQUIRE(mode == 0 || (normal && pose), "g2s_sweep_shade: mode %d needs normal and pose", mode);
+    G2S_REQUIRE((mode != 1 && mode != 2) || light, "g2s_sweep_shade: mode %d needs light", mode);
+    ShadeParams p{};
+    p.verts = verts;
+    p.faces = faces;
+    p.face_idx = face_idx;
+    p.bary = bary;
+    p.attr = attr;
+    p.normal = normal;
+    p.pose = pose;
+    p.light = light;
+    p.out = rgb_out;
+    p.alpha = alpha_out;
+    p.B = B;
+    p.V = V;
+    p.N = n_verts;
+    p.F = n_faces;
+    p.S = S;
+    p.is = S * ssaa;
+    p.ssaa = ssaa;
+    p.C = reads_attr ? C : 3;
+    p.Cout = reads_attr ? C : 3;
+    p.fill_back = fill_back ? 1 : 0;
+    p.grey = grey;
+    for (int c = 0; c < p.Cout; c++) p.bg[c] = background[c];
+    if (faces) launch_shade<false>(p, mode, as_stream(stream));
+    else launch_shade<true>(p, mode, as_stream(stream));
+    return check_launch("g2s_sweep_shade");
+}

@@ -526,3 +526,158 @@ class Renderer:
                                              int(bool(self.fill_back)), None, 0.0, None, _lib.ptr(alpha),
                                              _lib.stream()))
         return alpha
+
+
+# ------------------------------------------------------------------------------------------ viewing path
+SWEEP_MODES = {"texture": 0, "shaded": 1, "shape": 2, "normal": 3}
+
+
+def _sweep_mode(mode):
+    if mode in SWEEP_MODES:
+        return SWEEP_MODES[mode]
+    if mode in SWEEP_MODES.values():
+        return int(mode)
+    raise ValueError(f"mode must be one of {list(SWEEP_MODES)} (or 0..3), got {mode!r}")
+
+
+def sweep_frames(verts, pose, faces, attr, normal, light, K, orig_size, image_size, anti_aliasing, fill_back, near,
+                 far, background, grey, mode, want_alpha=False, want_depth=False):
+    """The three launches of the viewing path beside RenderRgbFunction, without autograd (there is no backward):
+    g2s_sweep_verts (verts (B,N,3), pose (B,V,12) -> (B*V,N,3)), g2s_raster_depth_fwd over the B*V posed meshes,
+    g2s_sweep_shade (include/g2s.h).  attr (B,C,N...) / normal (B,N...,3) / light (B*V,5) may be None where the
+    mode does not read them; `faces` is (F,3) int32 or None (implicit regular grid).  Returns (rgb (B,V,Cout,S,S),
+    alpha (B,V,S,S) or None, depth (B,V,S,S) or None)."""
+    mode = _sweep_mode(mode)
+    _lib.require_cuda(verts, pose, faces, attr, normal, light)
+    with torch.no_grad():
+        verts = verts.float().contiguous()
+        pose = pose.float().contiguous()
+        B, N, _ = verts.shape
+        V = pose.shape[1]
+        if pose.shape != (B, V, 12):
+            raise ValueError(f"pose must be [B={B}, V, 12], got {tuple(pose.shape)}")
+        S = int(image_size)
+        ssaa = 2 if anti_aliasing else 1
+        fb = int(bool(fill_back))
+        if faces is not None:
+            faces = faces.int().contiguous()
+        elif N != S * S:
+            raise ValueError("regular-grid faces need S*S vertices")
+        F = 2 * (S - 1) * (S - 1) if faces is None else faces.shape[0]
+        C = 3
+        if mode in (0, 1):
+            if attr is None:
+                raise ValueError("modes texture and shaded read the image")
+            attr = attr.float().contiguous()
+            C = attr.shape[1]
+            if attr.shape[0] != B or attr[0, 0].numel() != N:
+                raise ValueError(f"attr must be [B={B}, C, Ha, Wa] with Ha*Wa = {N}, got {tuple(attr.shape)}")
+        else:
+            attr = None
+        if mode != 0:
+            if normal is None:
+                raise ValueError("modes shaded, shape and normal read the normals")
+            normal = normal.float().contiguous()
+            if normal.shape[0] != B or normal.numel() != B * N * 3:
+                raise ValueError(f"normal must be [B={B}, Ha, Wa, 3] with Ha*Wa = {N}, got {tuple(normal.shape)}")
+        else:
+            normal = None
+        if mode in (1, 2):
+            if light is None:
+                raise ValueError("modes shaded and shape need a light")
+            light = light.float().contiguous()
+            if light.numel() != B * V * 5:
+                raise ValueError(f"light must hold B*V = {B * V} rows of (la, lb, lx, ly, lz), got {tuple(light.shape)}")
+        else:
+            light = None
+        Cout = C if mode in (0, 1) else 3
+        bg = [float(v) for v in background][:Cout]
+        bg += [bg[-1]] * (Cout - len(bg))
+        L = _lib.load()
+        st = _lib.stream()
+        dev = verts.device
+        posed = torch.empty((B * V, N, 3), dtype=torch.float32, device=dev)
+        _lib.check(L.g2s_sweep_verts(_lib.ptr(verts), _lib.ptr(pose), _lib.ptr(posed), B, V, N, st))
+        depth = torch.empty((B * V, S, S), dtype=torch.float32, device=dev)
+        fidx = torch.empty((B * V, S * ssaa, S * ssaa), dtype=torch.int32, device=dev)
+        bary = torch.empty((B * V, S * ssaa, S * ssaa, 3), dtype=torch.float32, device=dev)
+        ws = _workspace(dev, L.g2s_raster_workspace_bytes(B * V, N, F, S))
+        Kc = (_lib.C.c_float * 9)(*K)
+        _lib.check(L.g2s_raster_depth_fwd(_lib.ptr(posed), _lib.ptr(faces), B * V, N, F, S, Kc, float(orig_size), ssaa,
+                                          fb, float(near), float(far), _lib.ptr(depth), _lib.ptr(fidx),
+                                          _lib.ptr(bary), _lib.ptr(ws), ws.numel(), st))
+        rgb = torch.empty((B, V, Cout, S, S), dtype=torch.float32, device=dev)
+        alpha = torch.empty((B, V, S, S), dtype=torch.float32, device=dev) if want_alpha else None
+        _lib.check(L.g2s_sweep_shade(_lib.ptr(posed), _lib.ptr(faces), _lib.ptr(fidx), _lib.ptr(bary), _lib.ptr(attr),
+                                     _lib.ptr(normal), _lib.ptr(pose), _lib.ptr(light), B, V, N, F, S, ssaa, C, fb,
+                                     mode, (_lib.C.c_float * Cout)(*bg), float(grey), _lib.ptr(rgb), _lib.ptr(alpha),
+                                     st))
+    return rgb, alpha, depth.view(B, V, S, S) if want_depth else None
+
+
+def sweep_shade_torch(verts, faces, face_idx, bary, attr, normal, pose, light, B, V, S, ssaa, fill_back, mode,
+                      background, grey=0.7):
+    """g2s_sweep_shade (include/g2s.h) written in torch ops, on any device and in the dtype of `verts`: the float32
+    comparator of the tests and the statement of what the kernel computes, operation by operation.  Arguments as the
+    kernel's: posed verts (B*V,N,3), faces (F,3) or None, face_idx (B*V,is,is), bary (B*V,is,is,3), attr (B,C,...),
+    normal (B,...,3), pose (B,V,12), light (B*V,5).  Returns (rgb (B*V,Cout,S,S), alpha (B*V,S,S))."""
+    mode = _sweep_mode(mode)
+    dev, dt = verts.device, verts.dtype
+    N = verts.shape[1]
+    if faces is None:
+        faces = _regular_grid_faces(S, dev)
+    faces = faces.long()
+    F = faces.shape[0]
+    isz = S * ssaa
+    fn = face_idx.long()
+    hit = fn >= 0
+    g = fn.clamp(min=0) % F
+    rev = (fn >= F) if fill_back else torch.zeros_like(hit)
+    vid = faces[g]                                                    # (BV, is, is, 3)
+    vid = torch.where(rev[..., None], vid.flip(-1), vid)
+    frame = torch.arange(B * V, device=dev).view(-1, 1, 1, 1)
+    image = frame // V
+    z = verts[..., 2][frame, vid]                                     # (BV, is, is, 3)
+    w = bary.to(dt)
+    depth = 1.0 / (w[..., 0] / z[..., 0] + w[..., 1] / z[..., 1] + w[..., 2] / z[..., 2])
+    u = w * depth[..., None] / z
+    C = 3
+    a = None
+    if mode in (0, 1):
+        C = attr.shape[1]
+        at = attr.reshape(B, C, N).to(dt)
+        src = at[image[..., None], torch.arange(C, device=dev).view(1, 1, 1, 1, C), vid[..., None]]   # (BV,is,is,3,C)
+        a = (u[..., 0, None] * src[..., 0, :] + u[..., 1, None] * src[..., 1, :]) + u[..., 2, None] * src[..., 2, :]
+    if mode == 0:
+        col = a
+    else:
+        nm = normal.reshape(B, N, 3).to(dt)[image, vid]                # (BV, is, is, 3 vertices, 3)
+        m = (u[..., 0, None] * nm[..., 0, :] + u[..., 1, None] * nm[..., 1, :]) + u[..., 2, None] * nm[..., 2, :]
+        A = pose.reshape(B * V, 12)[:, :9].to(dt).view(B * V, 1, 1, 3, 3)
+        n = (A[..., 0] * m[..., None, 0] + A[..., 1] * m[..., None, 1]) + A[..., 2] * m[..., None, 2]
+        length = ((n[..., 0] * n[..., 0] + n[..., 1] * n[..., 1]) + n[..., 2] * n[..., 2]).sqrt()
+        n = n / length.clamp(min=1e-12)[..., None]
+        if mode == 3:
+            col = n
+        else:
+            lt = light.reshape(B * V, 5).to(dt).view(B * V, 1, 1, 5)
+            dot = (n[..., 0] * lt[..., 2] + n[..., 1] * lt[..., 3]) + n[..., 2] * lt[..., 4]
+            shade = lt[..., 0] + lt[..., 1] * dot.clamp(min=0)
+            if mode == 1:
+                col = (a / 2.0 + 0.5) * shade[..., None] * 2.0 - 1.0
+            else:
+                col = (grey * shade * 2.0 - 1.0)[..., None].expand(-1, -1, -1, 3)
+    Cout = col.shape[-1]
+    bg = [float(v) for v in background][:Cout]
+    bg += [bg[-1]] * (Cout - len(bg))
+    col = torch.where(hit[..., None], col, torch.tensor(bg, dtype=dt, device=dev))
+    col = col.flip(1).view(B * V, S, ssaa, S, ssaa, Cout)              # vertical flip, then ssaa x ssaa blocks
+    cov = hit.flip(1).view(B * V, S, ssaa, S, ssaa).to(dt)
+    total = torch.zeros(B * V, S, S, Cout, dtype=dt, device=dev)
+    count = torch.zeros(B * V, S, S, dtype=dt, device=dev)
+    for dy in range(ssaa):                                            # the kernel's order: dy, then dx
+        for dx in range(ssaa):
+            total = total + col[:, :, dy, :, dx]
+            count = count + cov[:, :, dy, :, dx]
+    inv = 1.0 / float(ssaa * ssaa)
+    return (total * inv).permute(0, 3, 1, 2).contiguous(), count * inv

@@ -10,7 +10,8 @@ render_given_view (renderer.py:141-277) and downscale_K go through the texture p
 rasterizer (`render_rgb`); their pose sweeps share one helper (`_sweep`).  That path is
 differentiable: everything around `render_rgb` is torch ops, so render_given_view(im, depth, view,
 grid_sample=False) carries gradients to `im`, `depth` and `view` (gradient of the texture lookup,
-no silhouette term — plugins/neural_renderer.py).
+no silhouette term — plugins/neural_renderer.py).  render_sweep is the batched viewing path beside them (no gradient):
+all poses of a sweep in three launches (csrc/sweep.hip).
 """
 import math
 
@@ -268,6 +269,88 @@ class Renderer():
         poses = [(0., float(y), 0.) for y in yaw] + [(float(p), 0., 0.) for p in pitch]
         return self._sweep(im, depth, poses, v_before, None, grid_sample, verts)
 
+    # ------------------------------------------------------------------ viewing path (batched, no gradient)
+    def sweep_pose(self, rotations, v_before=None, v_after=None, b=1):
+        """(b, V, 12) = row-major A, then t, of every frame: the chain `_canonical_mesh` and `_sweep` apply one
+        step after another (undo of `v_before`, the sweep rotation about the rotation centre, `v_after`) composed
+        into one affine map per frame — see `compose_sweep_pose`."""
+        return compose_sweep_pose(rotations, v_before, v_after, self.rot_center_depth, b)
+
+    def render_sweep(self, im, depth, rotations, v_before=None, v_after=None, mode="texture", light=None,
+                     normal=None, faces=None, grey=0.7, background=None, return_alpha=False, return_depth=False,
+                     max_frames=None):
+        """All frames of a pose sweep of the depth mesh in three launches per chunk (g2s_sweep_verts,
+        g2s_raster_depth_fwd, g2s_sweep_shade; csrc/sweep.hip) -> (B, V, Cout, S, S), S = image_size.
+
+        im (B,C,h,w) and `normal` (B,h,w,3; default get_normal_from_depth(depth)) are read in place as per-vertex
+        attributes shared by the V frames of an image.  rotations: (V,3) or (B,V,3) angle triples in the convention
+        of get_transform_matrices; v_before (B,k) / v_after (B,k) or (V,B,k) as in render_yaw.  mode: "texture"
+        (the interpolated image), "shaded" ((im/2+0.5) * (la + lb max(0, n.l)) * 2 - 1, model.py get_shading with
+        `im` as albedo), "shape" (the same with the constant `grey`), "normal" (the rotated unit normal).  light:
+        (V,5) or (B,V,5) rows (la, lb, lx, ly, lz), direction in the frame's camera space, used as given.  faces:
+        None (the grid of get_face_idx; needs h = w = image_size) or one (F,3) int32 list for the batch.
+        background: Cout floats (default: the renderer's, white).  Runs under no_grad; frames are processed in
+        chunks of at most `max_frames` (default: what keeps the saved raster maps of a chunk under 256 MiB), and the
+        result does not depend on the chunking.  Returns rgb, then alpha (B,V,S,S) and depth (B,V,S,S) on request."""
+        from .. import lib as _lib
+        _lib.require_cuda(im, depth)
+        with torch.no_grad():
+            b, c, h, w = im.shape
+            dev = im.device
+            S = self.image_size
+            r = self.renderer
+            verts = self.depth_to_3d_grid(depth.float()).reshape(b, -1, 3)
+            pose = self.sweep_pose(torch.as_tensor(rotations, dtype=torch.float32, device=dev),
+                                   v_before, v_after, b)
+            V = pose.shape[1]
+            m = nr._sweep_mode(mode)
+            if m != 0 and normal is None:
+                normal = self.get_normal_from_depth(depth.float().contiguous())
+            if m in (1, 2):
+                if light is None:
+                    raise ValueError("modes shaded and shape need `light`: (V, 5) or (B, V, 5)")
+                light = torch.as_tensor(light, dtype=torch.float32, device=dev)
+                light = light.expand(b, V, 5) if light.dim() == 2 else light
+                if light.shape != (b, V, 5):
+                    raise ValueError(f"light must be (V, 5) or (B, V, 5) with V = {V}, got {tuple(light.shape)}")
+            else:
+                light = None
+            if faces is not None and faces.dim() == 3:
+                faces = r._shared_faces(faces, h * w, S)
+            bg = r.background_color if background is None else background
+            ssaa = 2 if r.anti_aliasing else 1
+            if max_frames is None:
+                per_frame = (S * ssaa) ** 2 * 16 + h * w * 12
+                max_frames = max(1, (256 << 20) // per_frame)
+            max_frames = int(max_frames)
+            if max_frames < 1:
+                raise ValueError("max_frames must be at least 1")
+            bc = min(b, max_frames)
+            vc = min(V, max(1, max_frames // bc))
+            K = r._host_K(r.K)
+            out = alpha = dmap = None
+            for b0 in range(0, b, bc):
+                for v0 in range(0, V, vc):
+                    sb, sv = slice(b0, b0 + bc), slice(v0, v0 + vc)
+                    rgb_c, alpha_c, depth_c = nr.sweep_frames(
+                        verts[sb], pose[sb, sv], faces, im[sb], None if normal is None else normal[sb],
+                        None if light is None else light[sb, sv].reshape(-1, 5), K, r.orig_size, S,
+                        r.anti_aliasing, r.fill_back, r.near, r.far, bg, grey, m, return_alpha, return_depth)
+                    if bc >= b and vc >= V:
+                        out, alpha, dmap = rgb_c, alpha_c, depth_c
+                        break
+                    if out is None:
+                        out = torch.empty((b, V) + tuple(rgb_c.shape[2:]), dtype=torch.float32, device=dev)
+                        alpha = torch.empty((b, V, S, S), dtype=torch.float32, device=dev) if return_alpha else None
+                        dmap = torch.empty((b, V, S, S), dtype=torch.float32, device=dev) if return_depth else None
+                    out[sb, sv] = rgb_c
+                    if return_alpha:
+                        alpha[sb, sv] = alpha_c
+                    if return_depth:
+                        dmap[sb, sv] = depth_c
+        result = (out,) + ((alpha,) if return_alpha else ()) + ((dmap,) if return_depth else ())
+        return result[0] if len(result) == 1 else result
+
     def render_given_view(self, im, depth, view, mask=None, grid_sample=True):
         """renderer.py:252-277: warp `im` (and `mask`) to `view` — by inverse-warp sampling
         (grid_sample=True, the training path) or by rendering the textured mesh."""
@@ -290,3 +373,36 @@ class Renderer():
                                                     align_corners=True)
             return warped_images, warped_mask
         return warped_images
+
+
+def compose_sweep_pose(rotations, v_before, v_after, rot_center_depth, b=1):
+    """The pose chain of Renderer._canonical_mesh / Renderer._sweep as ONE affine map per frame -> (b, V, 12):
+    row-major A (3x3), then t.  With c the rotation centre (0, 0, rot_center_depth), (R0, t0) = v_before, Ri the
+    sweep rotation of frame i and (R2, t2) = v_after (of that frame), the chain is
+        p1 = R0^T (p - t0 - c) + c,   p2 = Ri (p1 - c) + c,   p3 = R2 (p2 - c) + c + t2
+    so  A = R2 Ri R0^T  and  t = c + t2 - A (c + t0).  rotations: (V,3) or (b,V,3); v_before: (b,k) or None; v_after:
+    (b,k), (V,b,k) or None.  Small (b,V,3,3) torch products in the dtype and on the device of `rotations`: no host
+    synchronisation."""
+    rot = rotations
+    if rot.dim() == 2:
+        rot = rot.unsqueeze(0).expand(b, -1, -1)
+    V = rot.shape[1]
+    dt, dev = rot.dtype, rot.device
+    Ri, _ = get_transform_matrices(rot.reshape(b * V, 3))
+    A = Ri.view(b, V, 3, 3)
+    c = torch.zeros(3, dtype=dt, device=dev)
+    c[2] = rot_center_depth
+    inner = c.view(1, 1, 3).expand(b, V, 3)          # c + t0
+    outer = inner                                    # c + t2
+    if v_before is not None:
+        R0, t0 = get_transform_matrices(v_before.to(dt))
+        A = A.matmul(R0.transpose(2, 1).unsqueeze(1))
+        inner = inner + t0.view(b, 1, 3)
+    if v_after is not None:
+        va = v_after.to(dt)
+        va = va.unsqueeze(0).expand(V, -1, -1) if va.dim() == 2 else va          # (V, b, k)
+        R2, t2 = get_transform_matrices(va.reshape(V * b, -1))
+        A = R2.view(V, b, 3, 3).transpose(0, 1).matmul(A)
+        outer = outer + t2.view(V, b, 3).transpose(0, 1)
+    t = outer - A.matmul(inner.unsqueeze(-1)).squeeze(-1)
+    return torch.cat([A.reshape(b, V, 9), t], 2).contiguous()

@@ -220,6 +220,41 @@ int g2s_raster_rgba_bwd(const float *verts, const int32_t *faces, const int32_t 
                         float eps, float *grad_textures, float *grad_verts, float *grad_light, void *workspace,
                         size_t workspace_bytes, int acc_is_zero, g2s_stream_t stream);
 
+/* Viewing path (Renderer.render_sweep): V poses per image of the same mesh in three launches — g2s_sweep_verts,
+ * g2s_raster_depth_fwd over the B*V posed meshes, g2s_sweep_shade.  No backward.
+ *
+ * g2s_sweep_verts: out[b*V + v, n] = A[b,v] . verts[b, n] + t[b,v].
+ * verts [B, n_verts, 3] canonical camera space; pose [B, V, 12]: row-major 3x3 A, then t; out [B*V, n_verts, 3].
+ * B <= 65535. */
+int g2s_sweep_verts(const float *verts, const float *pose, float *out, int B, int V, int n_verts,
+                    g2s_stream_t stream);
+
+/* g2s_sweep_shade: attribute pass over the maps g2s_raster_depth_fwd saved for the B*V posed meshes (face_idx, bary at
+ * ssaa*S, as g2s_raster_rgb_fwd takes them; same flip and ssaa x ssaa average), without texture cubes: the image and
+ * the normals are per-vertex attributes of image b = f / V, shared by its V frames.
+ * verts      [B*V, n_verts, 3] posed (the output of g2s_sweep_verts)
+ * faces      [n_faces, 3] or NULL = implicit regular grid (n_verts == S*S, n_faces == 2*(S-1)*(S-1))
+ * attr       [B, C, n_verts] image or albedo (C 1..4); read in modes 0 and 1, may be NULL otherwise
+ * normal     [B, n_verts, 3] unit normals in the canonical frame; NULL allowed in mode 0
+ * pose       [B, V, 12] as above; only A is read, to rotate the normals; NULL allowed in mode 0
+ * light      [B*V, 5] = la, lb, lx, ly, lz, direction in the frame's camera space, used as given; modes 1 and 2
+ * fill_back  what g2s_raster_depth_fwd was given (winner ids >= n_faces are the reversed copies: v0 and v2 swapped)
+ * background HOST pointer, Cout floats;  grey: the constant albedo of mode 2
+ * rgb_out    [B*V, Cout, S, S], Cout = C in modes 0 and 1, 3 in modes 2 and 3;  alpha_out [B*V, S, S] or NULL
+ * Per sample with winner (v0, v1, v2), saved weights w and z of the POSED vertices:
+ *     D = 1 / sum_k w_k / z_k,  u_k = w_k D / z_k  (no clamp, no renormalisation)
+ *     a = sum_k u_k attr[b, :, v_k],  m = sum_k u_k normal[b, v_k],  n = A m / max(|A m|, 1e-12)
+ *     mode 0 texture  a
+ *     mode 1 shaded   (a / 2 + 0.5) * (la + lb * max(0, n . l)) * 2 - 1   (get_shading, GAN2Shape/model.py:355-358)
+ *     mode 2 shape    the same with `grey` in place of a / 2 + 0.5
+ *     mode 3 normal   n
+ * Samples without a winner take `background` and count 0 for alpha.  No atomics: bit-identical from run to run.
+ * Every check precedes the launch: a rejected call leaves the outputs untouched. */
+int g2s_sweep_shade(const float *verts, const int32_t *faces, const int32_t *face_idx, const float *bary,
+                    const float *attr, const float *normal, const float *pose, const float *light, int B, int V,
+                    int n_verts, int n_faces, int S, int ssaa, int C, int fill_back, int mode,
+                    const float *background, float grey, float *rgb_out, float *alpha_out, g2s_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * fused bias + activation.
  * Replaces fused.fused_bias_act(input, bias, refer, act, grad, alpha, scale)
