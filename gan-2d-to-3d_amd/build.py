@@ -22,6 +22,7 @@ SOURCES = {
     "raster_rgb.hip": ["-ffp-contract=off"],
     "sweep.hip": ["-ffp-contract=off"],          # the unfused order its torch statement (sweep_shade_torch) has
     "face_light.hip": ["-ffp-contract=off"],     # forward and backward agree on the sign of dot(n, direction)
+    "mapping.hip": ["-ffp-contract=off"],        # the quantiser and the epilogues round as their torch expressions do
     "fused_bias_act.hip": [],
     "upfirdn2d.hip": [],
     "modconv.hip": [],

@@ -255,6 +255,35 @@ int g2s_sweep_shade(const float *verts, const int32_t *faces, const int32_t *fac
                     int n_verts, int n_faces, int S, int ssaa, int C, int fill_back, int mode,
                     const float *background, float grey, float *rgb_out, float *alpha_out, g2s_stream_t stream);
 
+/* Sample generator (generate.py): the mapping network in one launch, the ordered mean, the image quantiser.
+ * No backward.
+ *
+ * g2s_mapping_fwd: per row of z, in this order
+ *     h = z * rsqrt(mean_d(z^2) + 1e-8)                      if pixel_norm
+ *     L times:  h = gain * leaky_relu(h W_l^T + b_l, alpha)
+ *     out = center + truncation * (h - center)               if center != NULL
+ * z [N, D];  w [L, D, D] already multiplied by EqualLinear.scale, row = output feature (as F.linear takes it);
+ * b [L, D] already multiplied by lr_mul;  center [D] or NULL;  out [N, D].
+ * partial: NULL, or [ceil(N / T), D] with T the tile height the mapping-tile query below returns; row t receives
+ * the column sums of `out` over the rows of tile t (rows t*T .. min(N, (t+1)*T) - 1, ascending).
+ * D a multiple of 32 in 32..512, 1 <= L <= 16, N >= 1; z, w and out 16-byte aligned.  Rows past N are neither read
+ * nor stored.  No atomics: a row's result depends on that row alone, and is the same from run to run. */
+int g2s_mapping_tile(void);
+int g2s_mapping_fwd(const float *z, const float *w, const float *b, const float *center, float *out,
+                    float *partial, int64_t N, int D, int L, int pixel_norm, float alpha, float gain,
+                    float truncation, g2s_stream_t stream);
+
+/* g2s_rows_mean: out[d] = (partial[0][d] + partial[1][d] + ... in ascending tile order) / N.  partial [tiles, D]
+ * as g2s_mapping_fwd wrote it; out [D].  One launch; the same bits on every run and in either mode of
+ * g2s_set_deterministic. */
+int g2s_rows_mean(const float *partial, float *out, int64_t tiles, int D, int64_t N, g2s_stream_t stream);
+
+/* g2s_image_to_u8: x [B, 3, H, W] f32 -> out [B, H, W, 3] uint8 with the arithmetic of torchvision's
+ * save_image(normalize=True, range=(-1, 1)), every step rounded to f32:
+ *     clamp(x, -1, 1);  (x + 1) / 2;  * 255 + 0.5;  clamp(0, 255);  truncate.
+ * NaN inputs give an unspecified byte. */
+int g2s_image_to_u8(const float *x, uint8_t *out, int64_t B, int H, int W, g2s_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * fused bias + activation.
  * Replaces fused.fused_bias_act(input, bias, refer, act, grad, alpha, scale)
