@@ -34,6 +34,7 @@ SOURCES = {
     "split_reduce.hip": [],
     "rowops.hip": [],
     "projector.hip": [],
+    "synth_batch.hip": [],
     "lpips.hip": [],
     "pool.hip": [],
     "losses.hip": [],

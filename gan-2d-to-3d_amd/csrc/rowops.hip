@@ -117,7 +117,9 @@ __global__ __launch_bounds__(256) void demod_bwd(const float *__restrict__ wsq,
 //               (d loss / d demod of the producer; its convolution output is recovered from x: the leaky ReLU is
 //               invertible, so the forward never stores the pre-activation)
 // replacing four passes (rows_dot_scale x 2, the accumulation of the two consumers' gradients, the gate) by one.
-// One wavefront per row; every operand is read once.
+// One wavefront per row; every operand is read once.  PS (g2s_synth_bwd_rows_ps): one noise map per sample, noise
+// [rows / channels, n] — a row reads the map of b = row / channels, in gdot only; every sum keeps its order.
+template <bool PS>
 __global__ __launch_bounds__(256) void synth_rows(const float *__restrict__ x, const float *__restrict__ g1,
                                                   const float *__restrict__ s1, const float *__restrict__ g2,
                                                   const float *__restrict__ s2, const float *__restrict__ noise,
@@ -134,6 +136,7 @@ __global__ __launch_bounds__(256) void synth_rows(const float *__restrict__ x, c
     const float a1 = s1[row], a2 = g2 ? s2[row] : 0.0f;
     const float nw = gdot ? noise_w[0] : 0.0f, bi = gdot ? bias[row % channels] : 0.0f;
     const float inv_gain = 1.0f / gain, inv_slope = 1.0f / slope;
+    if (PS && gdot) noise += (size_t)(row / channels) * n;
     float d1 = 0.0f, d2 = 0.0f, dg = 0.0f;
     auto one = [&](float xv, float gv1, float gv2, float nz) {
         d1 += xv * gv1;
@@ -292,19 +295,37 @@ extern "C" int g2s_channel_sum(const float *g, float *out, int B, int C, int n, 
     return check_launch("g2s_channel_sum");
 }
 
-extern "C" int g2s_synth_bwd_rows(const float *x, const float *g1, const float *s1, const float *g2, const float *s2,
-                                  const float *noise, const float *noise_w, const float *bias, const float *demod,
-                                  float *out, float *dot1, float *dot2, float *gdot, int rows, int channels, int n,
-                                  float slope, float gain, g2s_stream_t stream) {
+template <bool PS>
+static int synth_bwd_rows_launch(const float *x, const float *g1, const float *s1, const float *g2, const float *s2,
+                                 const float *noise, const float *noise_w, const float *bias, const float *demod,
+                                 float *out, float *dot1, float *dot2, float *gdot, int rows, int channels, int n,
+                                 float slope, float gain, g2s_stream_t stream) {
     G2S_REQUIRE(x && g1 && s1 && dot1 && rows > 0 && channels > 0 && n > 0, "x, g1, s1, dot1 must not be NULL; sizes positive");
     G2S_REQUIRE((g2 == nullptr) == (s2 == nullptr) && (g2 == nullptr) == (dot2 == nullptr), "g2, s2, dot2 come together");
     G2S_REQUIRE(!gdot || (noise && noise_w && bias && demod), "gdot needs noise, noise_w, bias, demod");
     G2S_REQUIRE(slope > 0.0f && gain > 0.0f, "slope and gain must be positive (the activation is inverted)");
     uintptr_t bits = (uintptr_t)x | (uintptr_t)g1 | (uintptr_t)g2 | (uintptr_t)out | (gdot ? (uintptr_t)noise : 0);
     const int vec = (n % 4 == 0) && (bits & 15) == 0;
-    synth_rows<<<cdiv(rows, 4), 256, 0, as_stream(stream)>>>(x, g1, s1, g2, s2, noise, noise_w, bias, demod, out, dot1,
-                                                               dot2, gdot, rows, channels, n, slope, gain, vec);
-    return check_launch("g2s_synth_bwd_rows");
+    if (PS) G2S_REQUIRE(rows % channels == 0, "rows must be a multiple of channels with one noise map per sample");
+    synth_rows<PS><<<cdiv(rows, 4), 256, 0, as_stream(stream)>>>(x, g1, s1, g2, s2, noise, noise_w, bias, demod, out,
+                                                                   dot1, dot2, gdot, rows, channels, n, slope, gain, vec);
+    return check_launch(PS ? "g2s_synth_bwd_rows_ps" : "g2s_synth_bwd_rows");
+}
+
+extern "C" int g2s_synth_bwd_rows(const float *x, const float *g1, const float *s1, const float *g2, const float *s2,
+                                  const float *noise, const float *noise_w, const float *bias, const float *demod,
+                                  float *out, float *dot1, float *dot2, float *gdot, int rows, int channels, int n,
+                                  float slope, float gain, g2s_stream_t stream) {
+    return synth_bwd_rows_launch<false>(x, g1, s1, g2, s2, noise, noise_w, bias, demod, out, dot1, dot2, gdot, rows,
+                                        channels, n, slope, gain, stream);
+}
+
+extern "C" int g2s_synth_bwd_rows_ps(const float *x, const float *g1, const float *s1, const float *g2, const float *s2,
+                                     const float *noise, const float *noise_w, const float *bias, const float *demod,
+                                     float *out, float *dot1, float *dot2, float *gdot, int rows, int channels, int n,
+                                     float slope, float gain, g2s_stream_t stream) {
+    return synth_bwd_rows_launch<true>(x, g1, s1, g2, s2, noise, noise_w, bias, demod, out, dot1, dot2, gdot, rows,
+                                       channels, n, slope, gain, stream);
 }
 
 extern "C" int g2s_rows_dot_scale(const float *a, const float *b, const float *s, const float *inv,

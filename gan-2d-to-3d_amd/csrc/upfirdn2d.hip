@@ -23,9 +23,12 @@ struct UpfirParams {
     float alpha, gain;
 };
 
-template <typename T> __device__ __forceinline__ float upfir_finish(const UpfirParams &p, float acc, int m, int oy, int ox) {
+// PS (g2s_upfirdn2d_nba_ps): one map per sample, noise [major / channels, out_h, out_w] — plane m reads the map of
+// b = m / channels; the arithmetic and its order are those of the shared map (PS = false: the code it always was).
+template <typename T, bool PS> __device__ __forceinline__ float upfir_finish(const UpfirParams &p, float acc, int m, int oy, int ox) {
     if (p.bias) {
-        acc += p.bias[m % p.channels] + p.noise_w[0] * p.noise[oy * p.out_w + ox];
+        const float *nz = PS ? p.noise + (size_t)(m / p.channels) * p.out_h * p.out_w : p.noise;
+        acc += p.bias[m % p.channels] + p.noise_w[0] * nz[oy * p.out_w + ox];
         acc = (acc > 0.0f ? acc : acc * p.alpha) * p.gain;
     }
     return acc;
@@ -48,7 +51,7 @@ template <> __device__ __forceinline__ void stf<__half>(__half *p, float v) { *p
 // TWX = 160 with TW = 128 covers 129..160-wide outputs (the discriminator's 129 x 129 blur) in one
 // tile per row band — lanes loop over x, only the first few take the second turn.
 // UP, DOWN apply to both axes; KH x KW <= 4x4 compile-time taps.
-template <typename T, int UP, int DOWN, int KH, int KW, int TW, int TH, int TWX = TW>
+template <typename T, int UP, int DOWN, int KH, int KW, int TW, int TH, int TWX = TW, bool PS = false>
 __global__ __launch_bounds__(256) void upfirdn2d_tiled(const T *__restrict__ x,
                                                        const float *__restrict__ k,
                                                        T *__restrict__ y, UpfirParams p) {
@@ -126,7 +129,7 @@ __global__ __launch_bounds__(256) void upfirdn2d_tiled(const T *__restrict__ x,
 #pragma unroll
                         for (int kx = 0; kx < KW; kx++) acc += win[r * DOWN + ky][kx] * kr[ky][kx];
                     if (oy0 + r < p.out_h)
-                        stf<T>(y + ((size_t)m * p.out_h + oy0 + r) * p.out_w + ox, upfir_finish<T>(p, acc, m, oy0 + r, ox));
+                        stf<T>(y + ((size_t)m * p.out_h + oy0 + r) * p.out_w + ox, upfir_finish<T, PS>(p, acc, m, oy0 + r, ox));
                 }
             }
             }
@@ -150,7 +153,7 @@ __global__ __launch_bounds__(256) void upfirdn2d_tiled(const T *__restrict__ x,
                     const int ky = ky0 + j * UP, kx = kx0 + i * UP;
                     if (ky < KH && kx < KW) acc += sx[ry0 + j][rx0 + i] * sk[ky][kx];
                 }
-            stf<T>(y + ((size_t)m * p.out_h + oy) * p.out_w + ox, upfir_finish<T>(p, acc, m, oy, ox));
+            stf<T>(y + ((size_t)m * p.out_h + oy) * p.out_w + ox, upfir_finish<T, PS>(p, acc, m, oy, ox));
         }
         }
         }
@@ -158,7 +161,7 @@ __global__ __launch_bounds__(256) void upfirdn2d_tiled(const T *__restrict__ x,
 }
 
 // Generic fallback (any up/down per axis, any kernel size): one thread per output.
-template <typename T>
+template <typename T, bool PS>
 __global__ __launch_bounds__(256) void upfirdn2d_generic(const T *__restrict__ x,
                                                          const float *__restrict__ k,
                                                          T *__restrict__ y, UpfirParams p) {
@@ -180,45 +183,45 @@ __global__ __launch_bounds__(256) void upfirdn2d_generic(const T *__restrict__ x
                        k[(p.kh - 1 - ky) * p.kw + (p.kw - 1 - kx)];
             }
         }
-        stf<T>(y + i, upfir_finish<T>(p, acc, m, oy, ox));
+        stf<T>(y + i, upfir_finish<T, PS>(p, acc, m, oy, ox));
     }
 }
 
-template <typename T, int UP, int DOWN, int KH, int KW>
+template <typename T, bool PS, int UP, int DOWN, int KH, int KW>
 static void launch_tiled(const T *x, const float *k, T *y, const UpfirParams &p, hipStream_t st) {
     if (UP == 1 && p.out_w > 128 && p.out_w <= 160) {
         constexpr int TW = 128, TH = 16, TWX = 160;
         const int tiles = cdiv(p.out_w, TWX) * cdiv(p.out_h, TH);
         const int gy = std::min(p.major, std::max(1, 2048 / tiles));
-        upfirdn2d_tiled<T, UP == 1 ? UP : 1, DOWN, KH, KW, TW, TH, TWX><<<dim3(tiles, gy), dim3(TW, 256 / TW), 0, st>>>(x, k, y, p);
+        upfirdn2d_tiled<T, UP == 1 ? UP : 1, DOWN, KH, KW, TW, TH, TWX, PS><<<dim3(tiles, gy), dim3(TW, 256 / TW), 0, st>>>(x, k, y, p);
     } else if (UP == 1 && p.out_w >= 96) {
         constexpr int TW = 128, TH = 16;
         const int tiles = cdiv(p.out_w, TW) * cdiv(p.out_h, TH);
         const int gy = std::min(p.major, std::max(1, 2048 / tiles));
-        upfirdn2d_tiled<T, UP == 1 ? UP : 1, DOWN, KH, KW, TW, TH><<<dim3(tiles, gy), dim3(TW, 256 / TW), 0, st>>>(x, k, y, p);
+        upfirdn2d_tiled<T, UP == 1 ? UP : 1, DOWN, KH, KW, TW, TH, TW, PS><<<dim3(tiles, gy), dim3(TW, 256 / TW), 0, st>>>(x, k, y, p);
     } else if (UP == 1 && p.out_w >= 48) {
         constexpr int TW = 64, TH = 16;
         const int tiles = cdiv(p.out_w, TW) * cdiv(p.out_h, TH);
         const int gy = std::min(p.major, std::max(1, 2048 / tiles));
-        upfirdn2d_tiled<T, UP == 1 ? UP : 1, DOWN, KH, KW, TW, TH><<<dim3(tiles, gy), dim3(TW, 256 / TW), 0, st>>>(x, k, y, p);
+        upfirdn2d_tiled<T, UP == 1 ? UP : 1, DOWN, KH, KW, TW, TH, TW, PS><<<dim3(tiles, gy), dim3(TW, 256 / TW), 0, st>>>(x, k, y, p);
     } else {
         constexpr int TW = 32, TH = 32;
         const int tiles = cdiv(p.out_w, TW) * cdiv(p.out_h, TH);
         const int gy = std::min(p.major, std::max(1, 2048 / tiles));
-        upfirdn2d_tiled<T, UP, DOWN, KH, KW, TW, TH><<<dim3(tiles, gy), dim3(TW, 256 / TW), 0, st>>>(x, k, y, p);
+        upfirdn2d_tiled<T, UP, DOWN, KH, KW, TW, TH, TW, PS><<<dim3(tiles, gy), dim3(TW, 256 / TW), 0, st>>>(x, k, y, p);
     }
 }
 
-template <typename T>
+template <typename T, bool PS>
 static int dispatch(const T *x, const float *k, T *y, const UpfirParams &p, hipStream_t st) {
     const bool sq = p.up_x == p.up_y && p.down_x == p.down_y;
     const int up = p.up_x, down = p.down_x;
-    if (sq && p.kh == 4 && p.kw == 4 && up == 1 && down == 1) launch_tiled<T, 1, 1, 4, 4>(x, k, y, p, st);
-    else if (sq && p.kh == 4 && p.kw == 4 && up == 2 && down == 1) launch_tiled<T, 2, 1, 4, 4>(x, k, y, p, st);
-    else if (sq && p.kh == 4 && p.kw == 4 && up == 1 && down == 2) launch_tiled<T, 1, 2, 4, 4>(x, k, y, p, st);
+    if (sq && p.kh == 4 && p.kw == 4 && up == 1 && down == 1) launch_tiled<T, PS, 1, 1, 4, 4>(x, k, y, p, st);
+    else if (sq && p.kh == 4 && p.kw == 4 && up == 2 && down == 1) launch_tiled<T, PS, 2, 1, 4, 4>(x, k, y, p, st);
+    else if (sq && p.kh == 4 && p.kw == 4 && up == 1 && down == 2) launch_tiled<T, PS, 1, 2, 4, 4>(x, k, y, p, st);
     else {
         const long total = (long)p.major * p.out_h * p.out_w;
-        upfirdn2d_generic<T><<<std::min(cdiv(total, 256), 8192), 256, 0, st>>>(x, k, y, p);
+        upfirdn2d_generic<T, PS><<<std::min(cdiv(total, 256), 8192), 256, 0, st>>>(x, k, y, p);
     }
     return check_launch("g2s_upfirdn2d");
 }
@@ -230,7 +233,8 @@ using namespace g2s;
 static int upfirdn2d_launch(const void *x, const float *k, void *y, int major, int in_h, int in_w,
                             int kh, int kw, int up_x, int up_y, int down_x, int down_y, int pad_x0,
                             int pad_x1, int pad_y0, int pad_y1, int dtype, g2s_stream_t stream, int channels,
-                            const float *bias, const float *noise, const float *noise_w, float alpha, float gain) {
+                            const float *bias, const float *noise, const float *noise_w, float alpha, float gain,
+                            bool per_sample = false) {
     G2S_REQUIRE(x && k && y, "x, k, y must not be NULL");
     G2S_REQUIRE(major > 0 && in_h > 0 && in_w > 0 && kh > 0 && kw > 0, "sizes must be positive");
     G2S_REQUIRE(up_x > 0 && up_y > 0 && down_x > 0 && down_y > 0, "up/down must be positive");
@@ -257,8 +261,9 @@ static int upfirdn2d_launch(const void *x, const float *k, void *y, int major, i
     p.out_w = (in_w * up_x + pad_x0 + pad_x1 - kw + down_x) / down_x;
     G2S_REQUIRE(p.out_h > 0 && p.out_w > 0, "empty output (%d x %d)", p.out_h, p.out_w);
     hipStream_t st = as_stream(stream);
-    if (dtype == G2S_F32) return dispatch<float>((const float *)x, k, (float *)y, p, st);
-    return dispatch<__half>((const __half *)x, k, (__half *)y, p, st);
+    if (per_sample) return dispatch<float, true>((const float *)x, k, (float *)y, p, st);   // f32 only: checked by its entry
+    if (dtype == G2S_F32) return dispatch<float, false>((const float *)x, k, (float *)y, p, st);
+    return dispatch<__half, false>((const __half *)x, k, (__half *)y, p, st);
 }
 
 extern "C" int g2s_upfirdn2d(const void *x, const float *k, void *y, int major, int in_h, int in_w,
@@ -281,3 +286,14 @@ extern "C" int g2s_upfirdn2d_nba(const float *x, const float *k, float *y, int m
                             G2S_F32, stream, channels, bias, noise, noise_w, alpha, gain);
 }
 
+
+// g2s_upfirdn2d_nba with ONE MAP PER SAMPLE: noise [B = major / channels, out_h, out_w], plane m reads map m / channels.
+extern "C" int g2s_upfirdn2d_nba_ps(const float *x, const float *k, float *y, int major, int channels, int in_h, int in_w,
+                                    int kh, int kw, int up, int down, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
+                                    const float *bias, const float *noise, const float *noise_w, float alpha, float gain,
+                                    g2s_stream_t stream) {
+    G2S_REQUIRE(bias && noise && noise_w && channels > 0 && major % channels == 0,
+                "bias, noise, noise_w must not be NULL; major must be a multiple of channels");
+    return upfirdn2d_launch(x, k, y, major, in_h, in_w, kh, kw, up, up, down, down, pad_x0, pad_x1, pad_y0, pad_y1,
+                            G2S_F32, stream, channels, bias, noise, noise_w, alpha, gain, true);
+}

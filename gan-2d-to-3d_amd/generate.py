@@ -3,7 +3,7 @@ which made GAN2Shape's car, cat and church data: every image comes with the late
 projection is needed.
 
     python -m gan2shape_amd.generate --ckpt <file> --size 128 --channel-multiplier 1 --out <root>/<category>
-           [--pics 20] [--sample 1] [--truncation 0.7] [--truncation-mean 4096] [--seed 0] [--device cuda]
+           [--pics 20] [--sample 1] [--batched] [--truncation 0.7] [--truncation-mean 4096] [--seed 0] [--device cuda]
 
 Written under --out, ready for `dataset.ImageLatentDataset(<out>)`:
     %06d.png          --pics * --sample images
@@ -16,8 +16,9 @@ their bias + leaky ReLU and the truncation lerp, the activations of a 16-row til
 on every run), and the images are quantised by g2s_image_to_u8 with save_image's arithmetic, so that a quarter of
 the bytes crosses to the host.  Noise follows the reference's default (randomize_noise=True): one [n, 1, r, r] normal
 draw per styled layer, in layer order.  The fused epilogues of the one-node generator read ONE noise map per launch
-(DESIGN.md §4.13), so each sample goes through Generator.forward on its own with [1, 1, r, r] views of those draws;
-per-sample noise inside the epilogues is not built.  CPU tensors take plain torch ops throughout, as in
+(DESIGN.md §4.13), so by default each sample goes through Generator.forward on its own with [1, 1, r, r] views of those
+draws; --batched (sample(batched=True)) runs ONE forward for the n samples on the [n, 1, r, r] draws through the
+one-node path with one map per sample (synthesis.per_sample_noise).  CPU tensors take plain torch ops throughout, as in
 op/cpu_tensors.py.  `Generator.style_forward`, `Generator.mean_latent` and `projector.mean_latent_stats` are
 unchanged: training's latent projection needs the mapping backward, which this kernel does not have.
 """
@@ -168,30 +169,36 @@ def draw(G, n, generator=None):
     return z, [torch.randn(n, 1, r, r, device=device, generator=generator) for r in noise_sides(G)]
 
 
-def sample(G, n, truncation=1.0, mean_latent=None, generator=None, draws=None):
+def sample(G, n, truncation=1.0, mean_latent=None, generator=None, draws=None, batched=False):
     """(images [n, 3, S, S], w [n, D]) with w the truncated latent.  `draws`: the (z, noise maps) to use instead of
     fresh ones from `draw`.  Each sample is one Generator.forward with its own [1, 1, r, r] noise views (the one-node
-    path on a frozen generator on the device)."""
+    path on a frozen generator on the device); batched: ONE Generator.forward for all n on the [n, 1, r, r] draws (the
+    one-node path with one map per sample on the device, the layer loop on CPU tensors).  The draws are the same."""
     with torch.no_grad():
         z, noise = draw(G, n, generator) if draws is None else draws
         center = mean_latent if truncation < 1 else None
         if truncation < 1 and center is None:
             raise ValueError("sample: truncation < 1 needs the mean latent")
         w = map_latents(G, z, center=center, truncation=truncation)
+        if batched:
+            from . import synthesis
+            with synthesis.per_sample_noise():
+                return G([w], input_is_w=True, noise=list(noise))[0], w
         images = [G([w[i:i + 1]], input_is_w=True, noise=[m[i:i + 1] for m in noise])[0] for i in range(n)]
         return torch.cat(images), w
 
 
 # --------------------------------------------------------------------------------------------------------- command
-def write_samples(G, out_dir, pics, per_batch=1, truncation=0.7, truncation_mean=4096, generator=None, log=None):
+def write_samples(G, out_dir, pics, per_batch=1, truncation=0.7, truncation_mean=4096, generator=None, log=None,
+                  batched=False):
     """What the command does after G is built: pics * per_batch samples into `out_dir` in ImageLatentDataset's
-    layout.  Returns the image names."""
+    layout; batched: each chunk of per_batch samples is one forward (`sample`).  Returns the image names."""
     from PIL import Image
     os.makedirs(os.path.join(out_dir, "latents"), exist_ok=True)
     center = mean_latent(G, truncation_mean, generator) if truncation < 1 else None
     names = []
     for _ in range(pics):
-        images, w = sample(G, per_batch, truncation, center, generator)
+        images, w = sample(G, per_batch, truncation, center, generator, batched=batched)
         pixels = image_to_u8(images).cpu().numpy()
         w = w.cpu()
         for j in range(per_batch):
@@ -215,6 +222,8 @@ def build_parser():
     parser.add_argument("--out", required=True, help="<root>/<category>: the dataset directory to write")
     parser.add_argument("--pics", type=int, default=20, help="number of batches")
     parser.add_argument("--sample", type=int, default=1, help="samples per batch")
+    parser.add_argument("--batched", action="store_true",
+                        help="one generator forward per batch of --sample images instead of one per image")
     parser.add_argument("--truncation", type=float, default=0.7)
     parser.add_argument("--truncation-mean", dest="truncation_mean", type=int, default=4096,
                         help="draws behind the mean latent (not computed with --truncation 1)")
@@ -235,7 +244,7 @@ def main(argv=None, G=None):
     G = G.to(device).eval().requires_grad_(False)
     generator = torch.Generator(device=device).manual_seed(args.seed)
     return write_samples(G, args.out, args.pics, args.sample, args.truncation, args.truncation_mean, generator,
-                         log=print)
+                         log=print, batched=args.batched)
 
 
 if __name__ == "__main__":

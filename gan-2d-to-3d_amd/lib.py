@@ -55,11 +55,14 @@ SIGNATURES = {
     "g2s_maxpool2x2_bwd": (_i, [_p, _p, _p, _i64, _i, _i, _p]),
     "g2s_add_bias_scale": (_i, [_p, _p, _p, _p, _i64, _i64, _i, _f, _p]),
     "g2s_noise_bias_act": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _f, _f, _p]),
+    "g2s_noise_bias_act_ps": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _f, _f, _p]),
     "g2s_upfirdn2d": (_i, [_p, _p, _p] + [_i] * 14 + [_p]),
     "g2s_modconv": (_i, [_p] * 8 + [_i] * 9 + [_f, _f, _i, _p]),
     "g2s_modconv_needs_zero": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
     "g2s_upfirdn2d_nba": (_i, [_p, _p, _p] + [_i] * 12 + [_p, _p, _p, _f, _f, _p]),
     "g2s_synth_bwd_rows": (_i, [_p] * 13 + [_i, _i, _i, _f, _f, _p]),
+    "g2s_upfirdn2d_nba_ps": (_i, [_p, _p, _p] + [_i] * 12 + [_p, _p, _p, _f, _f, _p]),
+    "g2s_synth_bwd_rows_ps": (_i, [_p] * 13 + [_i, _i, _i, _f, _f, _p]),
     "g2s_channel_sum": (_i, [_p, _p, _i, _i, _i, _p]),
     "g2s_noise_grad": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "g2s_noise_regularize_workspace_bytes": (_sz, [_p, _i, _i]),

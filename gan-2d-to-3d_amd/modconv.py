@@ -367,7 +367,8 @@ class ModConvDemodFunction(Function):
 def modconv_demod(x, w, s, wsq, eps=1e-8, mode=PLAIN):
     """modconv(x, w, s, demodulation(s, wsq, eps), mode); one node when wsq is a constant."""
     if not x.is_cuda:          # CPU tensors: plain torch (op/cpu_tensors.py's rule)
-        return modconv(x, w, s, torch.rsqrt(s.pow(2) @ wsq.t() + eps), mode)
+        from .op import cpu_tensors
+        return cpu_tensors.modconv_demod(x, w, s, eps, mode)
     if wsq.requires_grad:
         return modconv(x, w, s, demodulation(s, wsq, eps), mode)
     _lib.require_cuda(s, wsq)

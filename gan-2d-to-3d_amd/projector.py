@@ -3,15 +3,18 @@ noise maps of a frozen generator against an image, with LPIPS + 1e5 * noise regu
 the reference's learning-rate ramp, latent jitter and noise re-normalisation after every step.  Its result is the
 `latents/<stem>.pt` file that dataset.LatentDataset reads:
 
-    python -m gan2shape_amd.projector --ckpt G.pt --size 128 --channel_multiplier 1 root/img0.png root/img1.png
+    python -m gan2shape_amd.projector --ckpt G.pt --size 128 --channel_multiplier 1 [--batch N] root/img0.png root/img1.png
 
 What runs on the GPU: the generator as one autograd node with noise-map gradients (synthesis._Synthesis,
 g2s_noise_grad), the LPIPS node (lpips._VggLpips), the regulariser of ALL maps in three launches each way
 (g2s_noise_regularize: value and gradient together in forward), the re-normalisation of all maps in two
 (g2s_noise_normalize) and the one-launch Adam (optim.Adam).  CPU tensors take plain torch ops (op/cpu_tensors.py's rule).
 
-A batch of images is a loop over `project`: the reference's batch couples its images only through the regulariser's
-mean over the batch."""
+`project` takes one image.  `project_batch` (--batch N) is the reference's loop as the reference runs it on several
+files: B images in one batch with [B, 1, s, s] noise maps, the generator as ONE node with one map per sample
+(synthesis.per_sample_noise), one LPIPS, one regulariser, one Adam step and one re-normalisation per step.  As in the
+reference the images of a batch are coupled: the regulariser's means and the re-normalisation's mean and standard
+deviation run over all B maps of a layer, so a file's result depends on the files it shares a batch with."""
 import argparse
 import math
 import os
@@ -218,6 +221,69 @@ def project(G, percept, image, steps=1000, lr=0.1, noise=0.05, noise_ramp=0.75, 
             'history': history}
 
 
+def project_batch(G, percept, images, steps=1000, lr=0.1, noise=0.05, noise_ramp=0.75, noise_regularize=1e5, mse=0.0,
+                  w_plus=False, lr_rampup=0.05, lr_rampdown=0.25, latent_stats=None, generator=None):
+    """The loop of projector.py:166-227 for B images (B, 3, H, W) at once, as the reference runs it when it is given
+    several files: latent_in is [B, D] ([B, n_latent, D] with w_plus), the maps are [B, 1, s, s] normal draws, the
+    jitter is drawn per sample, the loss is percept(...).sum() over the batch + noise_regularize * regulariser (+ mse *
+    the mean squared error over the batch), one Adam over all of it, then noise_normalize_.  The regulariser's means and
+    the normalisation's statistics run OVER THE BATCH (the reference's behaviour): the B projections are coupled through
+    them, and a batch of B is not B runs of `project`.  On CUDA tensors the generator is the one-node path with one map
+    per sample (synthesis.per_sample_noise); CPU tensors take the layer loop.  With the same `generator` seed B = 1 draws
+    what `project` draws, in its order and shapes, and gives its result bit for bit in deterministic mode.
+
+    Returns what `project` returns with a leading B: {'img': (B, 3, S, S), 'latent': (B, D) or (B, n_latent, D),
+    'noise': [(B, 1, s, s)], 'history': [latent_in after every 100th step]} — detached.  `split_projection` gives the
+    per-image dictionaries that `save_projection` writes."""
+    from . import synthesis
+    if images.dim() != 4 or images.shape[0] < 1:
+        raise ValueError("project_batch takes images (B, 3, H, W)")
+    reg_weight, reg = noise_regularize, globals()["noise_regularize"]
+    device = G.input.input.device
+    images = images.to(device)
+    B = images.shape[0]
+    if latent_stats is None:
+        latent_stats = mean_latent_stats(G, generator=generator)
+    latent_mean, latent_std = latent_stats
+    latent_std = float(latent_std)
+    noises = [(n if B == 1 else n.new_empty((B,) + tuple(n.shape[1:]))).normal_(generator=generator).requires_grad_(True)
+              for n in G.make_noise()]
+    latent_in = latent_mean.detach().clone().unsqueeze(0).repeat(B, 1)
+    if w_plus:
+        latent_in = latent_in.unsqueeze(1).repeat(1, G.n_latent, 1)
+    latent_in = latent_in.contiguous().requires_grad_(True)
+    optimizer = _adam([latent_in] + noises, lr)
+    history = []
+    for i in range(steps):
+        t = i / steps
+        optimizer.param_groups[0]["lr"] = get_lr(t, lr, lr_rampdown, lr_rampup)
+        strength = latent_std * noise * max(0, 1 - t / noise_ramp) ** 2
+        latent_n = latent_noise(latent_in, strength, generator)
+        with synthesis.per_sample_noise():
+            img_gen = _generate(G, latent_n, noises)
+        loss = percept(img_gen, images).sum() + reg_weight * reg(noises)
+        if mse != 0:
+            loss = loss + mse * F.mse_loss(img_gen, images)
+        optimizer.zero_grad()
+        loss.backward()
+        optimizer.step()
+        noise_normalize_(noises)
+        if (i + 1) % 100 == 0:
+            history.append(latent_in.detach().clone())
+    with torch.no_grad(), synthesis.per_sample_noise():
+        img, _ = G([latent_in], input_is_w=True, noise=noises)
+    return {'img': img.detach(), 'latent': latent_in.detach().clone(), 'noise': [n.detach().clone() for n in noises],
+            'history': history}
+
+
+def split_projection(result):
+    """project_batch's result -> one dictionary per image in `project`'s layout: 'img' (1, 3, S, S), 'latent' (D,) or
+    (n_latent, D), 'noise' [(1, 1, s, s)], 'history' [(1, ...)]."""
+    return [{'img': result['img'][j:j + 1], 'latent': result['latent'][j].clone(),
+             'noise': [n[j:j + 1].clone() for n in result['noise']], 'history': [h[j:j + 1] for h in result['history']]}
+            for j in range(result['img'].shape[0])]
+
+
 def save_projection(root, filename, result):
     """Write `root/latents/<stem>.pt` = {filename: {'img', 'latent', 'noise'}} of detached CPU tensors, <stem> =
     filename up to its first dot — the name dataset.LatentDataset reads (and loads with weights_only=True).  The
@@ -260,6 +326,9 @@ def main(argv=None):
     parser.add_argument("--lpips_lin_weights", type=str, default=None, help="lpips/weights/v0.1/vgg.pth")
     parser.add_argument("--lpips_vgg_weights", type=str, default=None, help="torchvision vgg16 state dict")
     parser.add_argument("--device", type=str, default="cuda")
+    parser.add_argument("--batch", type=int, default=1,
+                        help="files projected together (the reference's batch: their noise statistics are shared); "
+                             "1: one file at a time")
     parser.add_argument("files", metavar="FILES", nargs="+", help="path to image files to be projected")
     args = parser.parse_args(argv)
 
@@ -271,20 +340,34 @@ def main(argv=None):
     G = G.to(device).eval().requires_grad_(False)
     percept = PerceptualLoss(model='net-lin', net='vgg', lin_weights_path=args.lpips_lin_weights,
                              vgg_weights_path=args.lpips_vgg_weights).to(device)
+    if args.batch < 1:
+        parser.error("--batch must be at least 1")
     stats = mean_latent_stats(G)
+    options = dict(steps=args.step, lr=args.lr, noise=args.noise, noise_ramp=args.noise_ramp,
+                   noise_regularize=args.noise_regularize, mse=args.mse, w_plus=args.w_plus, lr_rampup=args.lr_rampup,
+                   lr_rampdown=args.lr_rampdown, latent_stats=stats)
     paths = []
-    for path in args.files:
-        image = load_image(path, min(args.size, 256)).to(device)
-        result = project(G, percept, image, steps=args.step, lr=args.lr, noise=args.noise, noise_ramp=args.noise_ramp,
-                         noise_regularize=args.noise_regularize, mse=args.mse, w_plus=args.w_plus,
-                         lr_rampup=args.lr_rampup, lr_rampdown=args.lr_rampdown, latent_stats=stats)
-        p_loss = float(evaluate(G, percept, image, result['latent'], result['noise']))
-        out = save_projection(os.path.dirname(path) or ".", os.path.basename(path), result)
-        from PIL import Image
-        Image.fromarray(make_image(result['img'])[0]).save(os.path.splitext(os.path.basename(path))[0] + "-project.png")
-        print(f"{path}: perceptual {p_loss:.4f} -> {out}")
-        paths.append(out)
+    # --batch 1: one `project` per file; N > 1: the files N at a time through project_batch (the last group may be shorter)
+    for first in range(0, len(args.files), args.batch):
+        group = args.files[first:first + args.batch]
+        images = [load_image(path, min(args.size, 256)).to(device) for path in group]
+        if args.batch == 1:
+            results = [project(G, percept, images[0], **options)]
+        else:
+            results = split_projection(project_batch(G, percept, torch.cat(images), **options))
+        for path, image, result in zip(group, images, results):
+            paths.append(_write_result(G, percept, path, image, result))
     return paths
+
+
+def _write_result(G, percept, path, image, result):
+    """One file's outputs: latents/<stem>.pt, the preview image, the printed perceptual distance.  Returns the .pt path."""
+    from PIL import Image
+    p_loss = float(evaluate(G, percept, image, result['latent'], result['noise']))
+    out = save_projection(os.path.dirname(path) or ".", os.path.basename(path), result)
+    Image.fromarray(make_image(result['img'])[0]).save(os.path.splitext(os.path.basename(path))[0] + "-project.png")
+    print(f"{path}: perceptual {p_loss:.4f} -> {out}")
+    return out
 
 
 if __name__ == "__main__":

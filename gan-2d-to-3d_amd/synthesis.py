@@ -22,8 +22,17 @@ The latent projector (projector.py) optimises the noise maps too: maps that requ
 tensor inputs and get noise_w * (sum over channels of the pre-activation gradient the row pass already writes), one
 launch of g2s_noise_grad per map; the forward, and every call with maps that require none, is unchanged.
 
+Per-sample noise (the batched projector and sampler: projector.project_batch, generate.sample(batched=True)) is behind
+a switch, `per_sample_noise()`, off by default: with it a map may be [B, 1, H, W].  Such a layer runs its convolution
+with the scales only and then its tail with one map per sample — plain layers one in-place pass (g2s_noise_bias_act_ps:
+one extra read and write of that layer's output), up-sampling layers the Blur's store as before (g2s_upfirdn2d_nba_ps);
+the row pass reads the sample's map (g2s_synth_bwd_rows_ps) and the map's gradient keeps its [B, 1, H, W].  A [1, 1, H,
+W] map in the same call keeps the fused epilogue.  The convolution kernels are untouched.
+
 Same arithmetic as the op-by-op path up to fp32 summation order and the 1-ulp inversion of the activation
 in the demodulation gradient; tests/test_gpu_round4.py holds image and style gradients to that path."""
+import contextlib
+
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -32,6 +41,21 @@ from . import lib as _lib
 from .modconv import PLAIN, UP2, modconv_nba_raw, modconv_raw, rows_dot_scale
 from .op.fused_act import add_bias_scale
 from .op.upfirdn2d import upfirdn2d, upfirdn2d_adjoint
+
+
+PER_SAMPLE = False      # eligible() accepts [B, 1, H, W] noise maps (one per sample); set by per_sample_noise()
+
+
+@contextlib.contextmanager
+def per_sample_noise(on=True):
+    """Within the block Generator.forward takes the one-node path for noise maps of leading dimension 1 or B (a mix is
+    allowed).  The choice is made in forward: a backward that runs after the block follows what forward recorded."""
+    global PER_SAMPLE
+    prev, PER_SAMPLE = PER_SAMPLE, bool(on)
+    try:
+        yield
+    finally:
+        PER_SAMPLE = prev
 
 
 def _ptr_array(tensors):
@@ -62,28 +86,49 @@ def _demod_bwd_all(entries):
                                                _int_array([w.shape[0] for w in wsqs]), len(entries), B, _lib.stream()))
 
 
-def _blur_nba(yc, blur, act, noise, nw):
-    """Blur (model.py:75-91, pad of ModulatedConv2d's up-sampling branch) + NoiseInjection + FusedLeakyReLU."""
+def _check_map(noise, B, H, W):
+    if tuple(noise.shape) != (B, 1, H, W) or noise.dtype != torch.float32 or not noise.is_cuda:
+        raise RuntimeError(f"synthesis: noise map {tuple(noise.shape)} does not fit a [{B}, C, {H}, {W}] activation")
+
+
+def _blur_nba(yc, blur, act, noise, nw, ps=False):
+    """Blur (model.py:75-91, pad of ModulatedConv2d's up-sampling branch) + NoiseInjection + FusedLeakyReLU; ps: one map
+    per sample, noise [B, 1, oh, ow]."""
     B, C, H, W = yc.shape
     k = blur.kernel
     p0, p1 = blur.pad
     oh, ow = H + p0 + p1 - k.shape[0] + 1, W + p0 + p1 - k.shape[1] + 1
+    if ps:
+        _check_map(noise, B, oh, ow)
     y = torch.empty((B, C, oh, ow), dtype=torch.float32, device=yc.device)
-    _lib.check(_lib.load().g2s_upfirdn2d_nba(_lib.ptr(yc), _lib.ptr(k), _lib.ptr(y), B * C, C, H, W, k.shape[0], k.shape[1],
-                                             1, 1, p0, p1, p0, p1, _lib.ptr(act.bias), _lib.ptr(noise), _lib.ptr(nw),
-                                             float(act.negative_slope), float(act.scale), _lib.stream()))
+    L = _lib.load()
+    _lib.check((L.g2s_upfirdn2d_nba_ps if ps else L.g2s_upfirdn2d_nba)(_lib.ptr(yc), _lib.ptr(k), _lib.ptr(y), B * C, C, H, W, k.shape[0], k.shape[1],
+        1, 1, p0, p1, p0, p1, _lib.ptr(act.bias), _lib.ptr(noise), _lib.ptr(nw),
+        float(act.negative_slope), float(act.scale), _lib.stream()))
     return y
 
 
-def _rows(x, g1, s1, g2=None, s2=None, tail=None, demod=None, want_out=True):
-    """g2s_synth_bwd_rows -> (out, dot1, dot2, gdot); `tail` = (noise, noise_w, bias, slope, gain) of the producer."""
+def _noise_bias_act_ps_(y, tail):
+    """The StyledConv tail with one map per sample, in place on the convolution's output (g2s_noise_bias_act_ps)."""
+    B, C, H, W = y.shape
+    noise, nw, bias, slope, gain = tail
+    _check_map(noise, B, H, W)
+    _lib.check(_lib.load().g2s_noise_bias_act_ps(_lib.ptr(y), _lib.ptr(noise), _lib.ptr(nw), _lib.ptr(bias), _lib.ptr(y),
+                                                 B, C, H * W, float(slope), float(gain), _lib.stream()))
+    return y
+
+
+def _rows(x, g1, s1, g2=None, s2=None, tail=None, demod=None, want_out=True, ps=False):
+    """g2s_synth_bwd_rows -> (out, dot1, dot2, gdot); `tail` = (noise, noise_w, bias, slope, gain) of the producer;
+    ps: its noise is one map per sample (g2s_synth_bwd_rows_ps)."""
     B, C, H, W = x.shape
     noise, nw, bias, slope, gain = tail
     out = torch.empty_like(x) if want_out else None
     dot1 = torch.empty((B, C), dtype=torch.float32, device=x.device)
     dot2 = torch.empty_like(dot1) if g2 is not None else None
     gdot = torch.empty_like(dot1) if demod is not None else None
-    _lib.check(_lib.load().g2s_synth_bwd_rows(
+    L = _lib.load()
+    _lib.check((L.g2s_synth_bwd_rows_ps if ps else L.g2s_synth_bwd_rows)(
         _lib.ptr(x), _lib.ptr(g1), _lib.ptr(s1), _lib.ptr(g2), _lib.ptr(s2),
         _lib.ptr(noise if demod is not None else None), _lib.ptr(nw if demod is not None else None),
         _lib.ptr(bias if demod is not None else None), _lib.ptr(demod), _lib.ptr(out), _lib.ptr(dot1), _lib.ptr(dot2),
@@ -98,11 +143,12 @@ def _tail(sc, noise):
 
 def _noise_grad(g_pre, layer):
     """d loss / d noise map of a StyledConv from the gradient of its pre-activation (NoiseInjection, model.py:294-305:
-    pre = conv + weight * noise + bias with ONE map for the whole batch): weight * sum over channels — and samples."""
+    pre = conv + weight * noise + bias): weight * sum over channels — and over samples for ONE map for the whole batch;
+    a per-sample map keeps its [B, 1, H, W]."""
     B, C, H, W = g_pre.shape
     g = torch.empty((B, 1, H, W), dtype=torch.float32, device=g_pre.device)
     _lib.check(_lib.load().g2s_noise_grad(_lib.ptr(g_pre), _lib.ptr(layer['tail'][1]), _lib.ptr(g), B, C, H * W, _lib.stream()))
-    return (g if B == 1 else g.sum(0, keepdim=True)).view(layer['noise_shape'])
+    return (g if B == 1 or layer['ps'] else g.sum(0, keepdim=True)).view(layer['noise_shape'])
 
 
 class _Synthesis(Function):
@@ -134,14 +180,18 @@ class _Synthesis(Function):
             assert mods[n] is sc.conv
             n += 1
             tail = _tail(sc, nz)
+            ps = nz.shape[0] != 1         # one map per sample: eligible() lets it in only under per_sample_noise()
             if up:
                 yc = modconv_raw(x, w, s, demod, UP2, 0)
-                y = _blur_nba(yc, sc.conv.blur, sc.activate, tail[0], tail[1])
+                y = _blur_nba(yc, sc.conv.blur, sc.activate, tail[0], tail[1], ps)
+            elif ps:
+                yc = None
+                y = _noise_bias_act_ps_(modconv_raw(x, w, s, demod, PLAIN, 0), tail)
             else:
                 yc = None
                 y = modconv_nba_raw(x, w, s, demod, tail[2], tail[0], tail[1], tail[3], tail[4])
             layers.append(dict(up=up, sc=sc, w=w, wsq=wsq.contiguous(), s=s, demod=demod, x=x, yc=yc, y=y, tail=tail,
-                               noise_shape=nz.shape))
+                               noise_shape=nz.shape, ps=ps))
             return y
 
         def to_rgb(tr, x, skip):
@@ -184,9 +234,11 @@ class _Synthesis(Function):
             gxs_rgb = modconv_raw(g_rgb, T['w'], None, None, PLAIN, 1)
             pos_T = 1 if ri == 0 else 1 + 3 * ri
             if nxt is None:                                      # top level: ToRGB is the only consumer
-                g_pre, dot_T, _, gdot = _rows(a, gxs_rgb, T['s'], None, None, plain['tail'], plain['demod'])
+                g_pre, dot_T, _, gdot = _rows(a, gxs_rgb, T['s'], None, None, plain['tail'], plain['demod'],
+                                                   ps=plain['ps'])
             else:
-                g_pre, dot_U, dot_T, gdot = _rows(a, nxt[0], nxt[1], gxs_rgb, T['s'], plain['tail'], plain['demod'])
+                g_pre, dot_U, dot_T, gdot = _rows(a, nxt[0], nxt[1], gxs_rgb, T['s'], plain['tail'], plain['demod'],
+                                                       ps=plain['ps'])
                 U = nxt[2]
                 order.append((nxt[3], dot_U))
                 pending.append((U['wsq'], U['s'], U['demod'], U['gd'], dot_U))
@@ -230,11 +282,12 @@ class _Synthesis(Function):
 
 def eligible(G, x0, styles, noise):
     """The one-node path serves the frozen generator on the fp32 kernels with ONE noise map per layer for the whole
-    batch (the epilogues read a single [H * W] map); per-sample maps [B > 1, 1, H, W] take the layer loop."""
+    batch (the epilogues read a single [H * W] map); per-sample maps [B > 1, 1, H, W] take the layer loop — unless
+    per_sample_noise() is on: then each map is [1, 1, H, W] or [B, 1, H, W]."""
     from . import modconv as mc
     if mc.OPERANDS != "f32" or not x0.is_cuda or x0.dtype != torch.float32 or any(nz is None for nz in noise):
         return False
-    if any(nz.shape[0] != 1 for nz in noise):
+    if any(nz.shape[0] != 1 and not (PER_SAMPLE and nz.dim() == 4 and nz.shape[0] == x0.shape[0]) for nz in noise):
         return False
     if any(p.requires_grad for p in G.parameters()):
         return False

@@ -370,6 +370,13 @@ int g2s_clamp(const float *x, const float *g, float *y, int64_t n, float lo, flo
 int g2s_noise_bias_act(const float *x, const float *noise, const float *noise_w,
                        const float *bias, float *y, int B, int C, int HW, float alpha,
                        float scale, g2s_stream_t stream);
+/* The same tail with ONE MAP PER SAMPLE (csrc/synth_batch.hip; the batched projector and sampler, synthesis.py):
+ *     y[b,c,i] = scale * lrelu_alpha(x[b,c,i] + noise_w[0] * noise[b,i] + bias[c])
+ * x, y [B, C, HW] f32 (the same buffer is allowed); noise [B, HW], not NULL; bias [C] or NULL.  16-byte loads and stores
+ * when HW % 4 == 0 and x, y, noise are 16-byte aligned, a scalar path otherwise.  The additions and their order are
+ * those of g2s_noise_bias_act: B equal maps give its bits. */
+int g2s_noise_bias_act_ps(const float *x, const float *noise, const float *noise_w, const float *bias, float *y, int B,
+                          int C, int HW, float alpha, float scale, g2s_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * upfirdn2d.
@@ -388,6 +395,11 @@ int g2s_upfirdn2d(const void *x, const float *k, void *y, int major, int in_h, i
 int g2s_upfirdn2d_nba(const float *x, const float *k, float *y, int major, int channels, int in_h, int in_w, int kh,
                       int kw, int up, int down, int pad_x0, int pad_x1, int pad_y0, int pad_y1, const float *bias,
                       const float *noise, const float *noise_w, float alpha, float gain, g2s_stream_t stream);
+/* g2s_upfirdn2d_nba with ONE MAP PER SAMPLE: noise [B = major / channels, out_h, out_w]; plane m reads the map of
+ * b = m / channels.  The same kernel body and arithmetic: B equal maps give g2s_upfirdn2d_nba's bits. */
+int g2s_upfirdn2d_nba_ps(const float *x, const float *k, float *y, int major, int channels, int in_h, int in_w, int kh,
+                         int kw, int up, int down, int pad_x0, int pad_x1, int pad_y0, int pad_y1, const float *bias,
+                         const float *noise, const float *noise_w, float alpha, float gain, g2s_stream_t stream);
 
 
 
@@ -632,6 +644,13 @@ int g2s_synth_bwd_rows(const float *x, const float *g1, const float *s1, const f
                        const float *noise, const float *noise_w, const float *bias, const float *demod, float *out,
                        float *dot1, float *dot2, float *gdot, int rows, int channels, int n, float slope, float gain,
                        g2s_stream_t stream);
+/* g2s_synth_bwd_rows with ONE MAP PER SAMPLE: noise [B = rows / channels, n] (rows a multiple of channels); row r reads
+ * the map of b = r / channels, in gdot only.  The same kernel body: every sum keeps its order, no atomics, the same
+ * bits in either mode of g2s_set_deterministic, and B equal maps give g2s_synth_bwd_rows' bits. */
+int g2s_synth_bwd_rows_ps(const float *x, const float *g1, const float *s1, const float *g2, const float *s2,
+                          const float *noise, const float *noise_w, const float *bias, const float *demod, float *out,
+                          float *dot1, float *dot2, float *gdot, int rows, int channels, int n, float slope, float gain,
+                          g2s_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * The latent projector's additions to the frozen generator (csrc/projector.hip; stylegan2-pytorch/projector.py:16-44,

@@ -47,6 +47,25 @@ def alternating(fns, warmup, rounds, per_round):
     return [float(np.median(t)) for t in times]
 
 
+def alternating_rounds(fns, warmup, rounds, per_round):
+    """As `alternating`, but the median of each round per function: [[round medians] per function]."""
+    for fn in fns:
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    out = [[] for _ in fns]
+    for _ in range(rounds):
+        for i, fn in enumerate(fns):
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(per_round)]
+            for e0, e1 in ev:
+                e0.record()
+                fn()
+                e1.record()
+            torch.cuda.synchronize()
+            out[i].append(float(np.median([e0.elapsed_time(e1) for e0, e1 in ev])))
+    return out
+
+
 def main():
     quick = "--quick" in sys.argv
     out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
@@ -119,6 +138,20 @@ def main():
         (t_s,) = alternating([sample8], 3, rounds, max(2, per_round // 4))
         result["sample_g128_n8"] = {"ms": t_s, "samples_per_s": 8 / (t_s * 1e-3)}
         print(f"sample G(128) n=8: {t_s:8.2f} ms = {8 / (t_s * 1e-3):8.1f} samples/s", flush=True)
+
+        # one forward per sample against ONE forward for the n samples (sample(batched=True): per-sample noise maps on
+        # the one-node path), alternating
+        for n in (8, 32):
+            def per_sample(n=n):
+                return generate.sample(G, n, 0.7, center, gen)
+
+            def batched(n=n):
+                return generate.sample(G, n, 0.7, center, gen, batched=True)
+            per_sample_rounds = alternating_rounds([per_sample, batched], 3, rounds, max(2, per_round // 4))
+            for name, r in zip(("per_sample", "batched"), per_sample_rounds):
+                result[f"sample_g128_n{n}_{name}"] = {"ms_median": float(np.median(r)), "ms_min_round": min(r),
+                                                      "ms_max_round": max(r), "samples_per_s": n / (float(np.median(r)) * 1e-3)}
+                print(f"sample G(128) n={n} {name}: {float(np.median(r)):8.2f} ms (rounds {min(r):.2f} .. {max(r):.2f})", flush=True)
     if out_path:
         os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
         with open(out_path, "w") as f:

@@ -5,7 +5,12 @@ the one-launch Adam — against the op-by-op form: Generator.ONE_NODE = False pl
 rounds inside one process, each step timed by HIP events after a warm-up; medians and the spread over rounds are
 printed, then the device launches of one step of each form, counted by the profiler in a run of its own.
 
-    python tools/bench_projector.py [--size 128] [--steps 50] [--rounds 5] [--warmup 10] [--out profiles/FILE]"""
+    python tools/bench_projector.py [--size 128] [--steps 50] [--rounds 5] [--warmup 10] [--out profiles/FILE]
+
+--batch 1 2 4 8 measures instead the step of projector.project_batch at each B (per-sample noise maps on the one-node
+path) against the B = 1 step of projector.project, alternating in the same rounds, and counts each one's launches:
+
+    python tools/bench_projector.py --batch 1 2 4 8 --out profiles/project_batch_g128.json"""
 import argparse
 import json
 import os
@@ -52,6 +57,35 @@ class Stepper:
         sg2.Generator.ONE_NODE = True
 
 
+class BatchStepper:
+    """project_batch's state and step for B images (projector.py's loop body under synthesis.per_sample_noise)."""
+
+    def __init__(self, G, percept, target, stats, B, seed):
+        from gan2shape_amd import synthesis
+        self.switch = synthesis.per_sample_noise
+        self.G, self.percept, self.target = G, percept, target.repeat(B, 1, 1, 1).contiguous()
+        self.std = float(stats[1])
+        self.gen = torch.Generator(device="cuda").manual_seed(seed)
+        self.noises = [n.new_empty((B,) + tuple(n.shape[1:])).normal_(generator=self.gen).requires_grad_(True)
+                       for n in G.make_noise()]
+        self.latent = stats[0].detach().clone().unsqueeze(0).repeat(B, 1).contiguous().requires_grad_(True)
+        self.opt = projector._adam([self.latent] + self.noises, 0.1)
+        self.i = 0
+
+    def step(self, total=1000):
+        t = (self.i % total) / total
+        self.i += 1
+        self.opt.param_groups[0]["lr"] = projector.get_lr(t, 0.1)
+        strength = self.std * 0.05 * max(0, 1 - t / 0.75) ** 2
+        with self.switch():
+            img = projector._generate(self.G, projector.latent_noise(self.latent, strength, self.gen), self.noises)
+        loss = self.percept(img, self.target).sum() + 1e5 * projector.noise_regularize(self.noises)
+        self.opt.zero_grad()
+        loss.backward()
+        self.opt.step()
+        projector.noise_normalize_(self.noises)
+
+
 def timed(stepper, n):
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
     for e0, e1 in ev:
@@ -78,6 +112,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--batch", type=int, nargs="+", default=None,
+                    help="measure project_batch's step at these batch sizes against project's B = 1 step")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_projector needs a GPU"
     lib.load()
@@ -90,7 +126,15 @@ def main():
         if args.size > 256:
             f = args.size // 256
             target = target.reshape(1, 3, 256, f, 256, f).mean([3, 5])
-    forms = {"fused": Stepper(G, percept, target, stats, True, 1), "op_by_op": Stepper(G, percept, target, stats, False, 1)}
+    if args.batch:
+        forms = {"project_b1": Stepper(G, percept, target, stats, True, 1)}
+        forms.update({f"project_batch_b{B}": BatchStepper(G, percept, target, stats, B, 1) for B in args.batch})
+        what = (f"projector step, G({args.size}): project (B = 1) and project_batch at B = {args.batch}, ms per step (HIP "
+                f"events; median of {args.steps} steps per round, {args.rounds} alternating rounds, {args.warmup} warm-up "
+                "steps); ms_per_image = ms_median / B")
+    else:
+        forms, what = None, None
+    forms = forms or {"fused": Stepper(G, percept, target, stats, True, 1), "op_by_op": Stepper(G, percept, target, stats, False, 1)}
     for s in forms.values():
         for _ in range(args.warmup):
             s.step()
@@ -99,10 +143,14 @@ def main():
     for _ in range(args.rounds):                      # alternate the two forms: drift and neighbours hit both alike
         for k, s in forms.items():
             per_round[k].append(float(np.median(timed(s, args.steps))))
-    result = {"what": f"projector step, G({args.size}), B = 1, ms per step (HIP events; median of {args.steps} steps per "
+    result = {"what": what or f"projector step, G({args.size}), B = 1, ms per step (HIP events; median of {args.steps} steps per "
                       f"round, {args.rounds} alternating rounds, {args.warmup} warm-up steps)"}
     for k, v in per_round.items():
         result[k] = {"ms_median": float(np.median(v)), "ms_min_round": min(v), "ms_max_round": max(v)}
+        if args.batch:
+            B = 1 if k == "project_b1" else int(k.rsplit("b", 1)[1])
+            result[k].update({"B": B, "ms_per_image": float(np.median(v)) / B, "ms_per_image_min_round": min(v) / B,
+                              "ms_per_image_max_round": max(v) / B})
     for k, s in forms.items():
         try:
             result[k]["device_launches_per_step"] = launches(s)
