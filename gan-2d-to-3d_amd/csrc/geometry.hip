@@ -11,18 +11,14 @@
 // workgroup and added with one float atomic per workgroup and component.
 #include <algorithm>
 #include "g2s_common.h"
+#include "wave_sum.h"
 #include "normal_core.h"
 
 namespace g2s {
 
-__device__ __forceinline__ float wave_sum_g(float v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // Sum `v` over the 256 threads of the workgroup and atomically add it to *dst (thread 0).
 __device__ __forceinline__ void block_atomic_add(float v, float *dst, float *red) {
-    v = wave_sum_g(v);
+    v = wave_sum(v);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     __syncthreads();
     if (lane == 0) red[wave] = v;

@@ -18,16 +18,12 @@
 //
 // No atomics: results are deterministic.
 #include "g2s_common.h"
+#include "wave_sum.h"
 
 namespace g2s {
 
 constexpr int GN_THREADS = 256;
 constexpr int GN_SLICE = 4096;  // elements per stats workgroup: 4 float4 per thread
-
-__device__ __forceinline__ float wave_sum(float v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // sum over the 256 threads of a workgroup; every thread gets the result
 __device__ __forceinline__ float block_sum(float v, float *sm) {

@@ -4,7 +4,8 @@
 // (GAN2Shape/losses.py:6-51: loss = (|a - b| * mask.expand_as).sum() / mask.expand_as.sum(), which the
 // reference runs as sub, abs, expand, mul, two full-size sums and a division per level).  The
 // denominator C * sum(w) needs only the small weight map and stays on the host side (torch).
-// Backward: gx = sign(x - y) * w * coef[0]  (coef = incoming gradient / denominator, a device scalar).
+// Backward: gx = sign(x - y) * w * coef[0]  (coef = incoming gradient / denominator, a device scalar), and what joins
+// it in the discriminator-feature loss: one kernel (wl1_bwd) for the three backward entries.
 #include <algorithm>
 #include "g2s_common.h"
 
@@ -39,26 +40,6 @@ __global__ __launch_bounds__(WL1_THREADS) void wl1_fwd(const float *__restrict__
     }
     const float s = wl1_block_sum(acc, sm);
     if (threadIdx.x == 0) unsafeAtomicAdd(num, s);
-}
-
-__global__ __launch_bounds__(WL1_THREADS) void wl1_bwd(const float *__restrict__ x, const float *__restrict__ y,
-                                                       const float *__restrict__ w, const float *__restrict__ coef,
-                                                       float *__restrict__ gx, int C, int HW4, long total4) {
-    const float k = coef[0];
-    const float4 *x4 = reinterpret_cast<const float4 *>(x), *y4 = reinterpret_cast<const float4 *>(y);
-    const float4 *w4 = reinterpret_cast<const float4 *>(w);
-    float4 *g4 = reinterpret_cast<float4 *>(gx);
-    for (long i = (long)blockIdx.x * WL1_THREADS + threadIdx.x; i < total4; i += (long)gridDim.x * WL1_THREADS) {
-        const float4 a = x4[i], b = y4[i];
-        float4 m = make_float4(k, k, k, k);
-        if (w) {
-            const long plane = i / HW4;
-            const float4 ww = w4[(plane / C) * HW4 + (i - plane * HW4)];
-            m = make_float4(ww.x * k, ww.y * k, ww.z * k, ww.w * k);
-        }
-        auto sgn = [](float d) { return d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f); };   // torch: sign(0) = 0
-        g4[i] = make_float4(sgn(a.x - b.x) * m.x, sgn(a.y - b.y) * m.y, sgn(a.z - b.z) * m.z, sgn(a.w - b.w) * m.w);
-    }
 }
 
 // The same with the denominator in the pass: numden[0] += sum |x - y| * w, numden[1] += sum w (over b, c, p — the
@@ -104,46 +85,22 @@ __global__ __launch_bounds__(THREADS) void wl1_fwd2(const float *__restrict__ x,
     }
 }
 
-// gx = gadd + sign(x - y) * w * g[0] / den[0]   (gadd may be NULL)
-__global__ __launch_bounds__(WL1_THREADS) void wl1_bwd2(const float *__restrict__ x, const float *__restrict__ y,
-                                                        const float *__restrict__ w, const float *__restrict__ g,
-                                                        const float *__restrict__ den, const float *__restrict__ gadd,
-                                                        float *__restrict__ gx, int C, int HW4, long total4) {
-    const float k = g[0] / den[0];
-    const float4 *x4 = reinterpret_cast<const float4 *>(x), *y4 = reinterpret_cast<const float4 *>(y);
-    const float4 *w4 = reinterpret_cast<const float4 *>(w), *a4 = reinterpret_cast<const float4 *>(gadd);
-    float4 *g4 = reinterpret_cast<float4 *>(gx);
-    for (long i = (long)blockIdx.x * WL1_THREADS + threadIdx.x; i < total4; i += (long)gridDim.x * WL1_THREADS) {
-        const float4 a = x4[i], b = y4[i];
-        float4 m = make_float4(k, k, k, k);
-        if (w) {
-            const long plane = i / HW4;
-            const float4 ww = w4[(plane / C) * HW4 + (i - plane * HW4)];
-            m = make_float4(ww.x * k, ww.y * k, ww.z * k, ww.w * k);
-        }
-        auto sgn = [](float d) { return d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f); };   // torch: sign(0) = 0
-        float4 r = make_float4(sgn(a.x - b.x) * m.x, sgn(a.y - b.y) * m.y, sgn(a.z - b.z) * m.z, sgn(a.w - b.w) * m.w);
-        if (gadd) {
-            const float4 e = a4[i];
-            r = make_float4(e.x + r.x, e.y + r.y, e.z + r.z, e.w + r.w);
-        }
-        g4[i] = r;
-    }
-}
-
-// One launch for a level of the discriminator-feature loss's backward (losses._DFeatureL1):
+// The one backward kernel, behind all three entries.  In full (g2s_weighted_l1_bwd3) it is one launch for a level of
+// the discriminator-feature loss's backward (losses._DFeatureL1):
 //     gx      = (gadd + gadd2) * add_scale + sign(x - y) * w * g[0] / den[0]
 //               (the residual join (a + b) / sqrt(2) of the block above, stylegan2-pytorch/model.py:693-697, with this
 //                level's masked-L1 gradient; x == NULL: no L1 term; gadd / gadd2 may be NULL)
 //     gx_gate = gx * gain * (gate_ref > 0 ? 1 : slope)      (FusedLeakyReLU's backward of the block's conv2, optional)
-__global__ __launch_bounds__(WL1_THREADS) void wl1_bwd3(const float *__restrict__ x, const float *__restrict__ y,
+// den == NULL: the factor is g[0] alone (g2s_weighted_l1_bwd's coef).  g2s_weighted_l1_bwd2 is the case gadd2 == NULL,
+// add_scale = 1 (e * 1 + r is e + r bit for bit, as a product and a sum or as one fused operation), no gate.
+__global__ __launch_bounds__(WL1_THREADS) void wl1_bwd(const float *__restrict__ x, const float *__restrict__ y,
                                                         const float *__restrict__ w, const float *__restrict__ g,
                                                         const float *__restrict__ den, const float *__restrict__ gadd,
                                                         const float *__restrict__ gadd2, float add_scale,
                                                         float *__restrict__ gx, const float *__restrict__ gate_ref,
                                                         float slope, float gain, float *__restrict__ gx_gate, int C,
                                                         int HW4, long total4) {
-    const float k = x ? g[0] / den[0] : 0.0f;
+    const float k = x ? (den ? g[0] / den[0] : g[0]) : 0.0f;
     const float4 *x4 = reinterpret_cast<const float4 *>(x), *y4 = reinterpret_cast<const float4 *>(y);
     const float4 *w4 = reinterpret_cast<const float4 *>(w), *a4 = reinterpret_cast<const float4 *>(gadd);
     const float4 *b4 = reinterpret_cast<const float4 *>(gadd2), *r4 = reinterpret_cast<const float4 *>(gate_ref);
@@ -183,6 +140,17 @@ __global__ __launch_bounds__(WL1_THREADS) void wl1_bwd3(const float *__restrict_
 
 using namespace g2s;
 
+static int wl1_bwd_launch(const char *who, const float *x, const float *y, const float *w, const float *g,
+                          const float *den, const float *gadd, const float *gadd2, float add_scale, float *gx,
+                          const float *gate_ref, float slope, float gain, float *gx_gate, int B, int C, int HW,
+                          g2s_stream_t stream) {
+    const long total4 = (long)B * C * HW / 4;
+    const int blocks = (int)std::min<long>(cdiv(total4, WL1_THREADS * 4), 4096);
+    wl1_bwd<<<blocks, WL1_THREADS, 0, as_stream(stream)>>>(x, y, w, g, den, gadd, gadd2, add_scale, gx, gate_ref, slope,
+                                                           gain, gx_gate, C, HW / 4, total4);
+    return check_launch(who);
+}
+
 extern "C" int g2s_weighted_l1_bwd3(const float *x, const float *y, const float *w, const float *g, const float *den,
                                     const float *gadd, const float *gadd2, float add_scale, float *gx,
                                     const float *gate_ref, float slope, float gain, float *gx_gate, int B, int C, int HW,
@@ -193,11 +161,8 @@ extern "C" int g2s_weighted_l1_bwd3(const float *x, const float *y, const float 
     G2S_REQUIRE(!gadd2 || gadd, "gadd2 needs gadd");
     G2S_REQUIRE(gx || gx_gate, "no output");
     G2S_REQUIRE((gx_gate == nullptr) == (gate_ref == nullptr), "gx_gate and gate_ref come together");
-    const long total4 = (long)B * C * HW / 4;
-    const int blocks = (int)std::min<long>(cdiv(total4, WL1_THREADS * 4), 4096);
-    wl1_bwd3<<<blocks, WL1_THREADS, 0, as_stream(stream)>>>(x, y, w, g, den, gadd, gadd2, add_scale, gx, gate_ref, slope,
-                                                            gain, gx_gate, C, HW / 4, total4);
-    return check_launch("g2s_weighted_l1_bwd3");
+    return wl1_bwd_launch("g2s_weighted_l1_bwd3", x, y, w, g, den, gadd, gadd2, add_scale, gx, gate_ref, slope, gain,
+                          gx_gate, B, C, HW, stream);
 }
 
 static int wl1_check(const void *x, const void *y, int B, int C, int HW) {
@@ -223,10 +188,8 @@ extern "C" int g2s_weighted_l1_bwd(const float *x, const float *y, const float *
     int rc = wl1_check(x, y, B, C, HW);
     if (rc) return rc;
     G2S_REQUIRE(coef && gx, "NULL pointer argument");
-    const long total4 = (long)B * C * HW / 4;
-    const int blocks = (int)std::min<long>(cdiv(total4, WL1_THREADS * 4), 4096);
-    wl1_bwd<<<blocks, WL1_THREADS, 0, as_stream(stream)>>>(x, y, w, coef, gx, C, HW / 4, total4);
-    return check_launch("g2s_weighted_l1_bwd");
+    return wl1_bwd_launch("g2s_weighted_l1_bwd", x, y, w, coef, nullptr, nullptr, nullptr, 1.0f, gx, nullptr, 0.0f,
+                          0.0f, nullptr, B, C, HW, stream);
 }
 
 extern "C" int g2s_weighted_l1_fwd2(const float *x, const float *y, const float *w, float *numden, int B, int C,
@@ -249,8 +212,6 @@ extern "C" int g2s_weighted_l1_bwd2(const float *x, const float *y, const float 
     int rc = wl1_check(x, y, B, C, HW);
     if (rc) return rc;
     G2S_REQUIRE(g && den && gx, "NULL pointer argument");
-    const long total4 = (long)B * C * HW / 4;
-    const int blocks = (int)std::min<long>(cdiv(total4, WL1_THREADS * 4), 4096);
-    wl1_bwd2<<<blocks, WL1_THREADS, 0, as_stream(stream)>>>(x, y, w, g, den, gadd, gx, C, HW / 4, total4);
-    return check_launch("g2s_weighted_l1_bwd2");
+    return wl1_bwd_launch("g2s_weighted_l1_bwd2", x, y, w, g, den, gadd, nullptr, 1.0f, gx, nullptr, 0.0f, 0.0f,
+                          nullptr, B, C, HW, stream);
 }

@@ -19,6 +19,7 @@
 // E[delta^2] - E[delta]^2 keeps 1e-16 of E[delta^2] and p = c g gives rounding noise of the inputs, not of the sum.
 // The file is compiled with -ffp-contract=off: d2 / n - mean * mean is then exactly 0 for a single pixel.
 #include "g2s_common.h"
+#include "wave_sum.h"
 #include "normal_core.h"
 
 namespace g2s {
@@ -27,11 +28,6 @@ constexpr int MT_X = 32, MT_Y = 8;            // tile
 constexpr int MT_LX = MT_X + 2, MT_LY = MT_Y + 2;
 constexpr int MT_TERMS = 7;                   // n, sum |d|, sum d^2, sum delta, sum delta^2, n_mad, sum angle
 constexpr unsigned char PIX_VALID = 1, PIX_FINITE = 2;
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void depth_metrics_tiles(const float *__restrict__ pred, const float *__restrict__ gt,
                                                            const float *__restrict__ mask_pred,
@@ -107,7 +103,7 @@ __global__ __launch_bounds__(256) void depth_metrics_tiles(const float *__restri
     const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
     for (int k = 0; k < MT_TERMS; k++) {
-        const double v = wave_sum_f64(term[k]);
+        const double v = wave_sum(term[k]);
         if (lane == 0) red[wave][k] = v;
     }
     __syncthreads();
@@ -126,7 +122,7 @@ __global__ __launch_bounds__(64) void depth_metrics_finish(const double *__restr
 #pragma unroll
         for (int k = 0; k < MT_TERMS; k++) acc[k] += p[(size_t)t * MT_TERMS + k];
 #pragma unroll
-    for (int k = 0; k < MT_TERMS; k++) acc[k] = wave_sum_f64(acc[k]);
+    for (int k = 0; k < MT_TERMS; k++) acc[k] = wave_sum(acc[k]);
     if (lane != 0) return;
     float *o = out + (size_t)b * 5;
     const double n = acc[0];

@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <cstdint>
 #include "g2s_common.h"
+#include "wave_sum.h"
 
 namespace g2s {
 
@@ -81,11 +82,6 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const float *__restri
         }
     }
     y[i] = v;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 // One wave per output: its lanes stride over the bin, then a butterfly sum (one fixed order).

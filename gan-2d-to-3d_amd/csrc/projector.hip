@@ -20,6 +20,7 @@
 //                         map in ascending order (Chan's update, double) and rescales its chunk.
 // None of the sums depends on g2s_set_deterministic: there is one partition, and it has a fixed order.
 #include "g2s_common.h"
+#include "wave_sum.h"
 
 namespace g2s {
 
@@ -28,14 +29,9 @@ constexpr int NZ_CHUNK = 4096;           // elements per workgroup of the produc
 constexpr int NZ_TILE = 64;              // level-0 side of a pooling tile: 64 >> 6 = 1, the deepest level of side 512
 constexpr int NZ_MAX_LEVELS = 7;         // 512, 256, 128, 64, 32, 16, 8
 
-__device__ __forceinline__ float nz_wave_sum(float v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // sum over the workgroup, the same value in every thread; `red` holds 4 floats
 __device__ __forceinline__ float nz_block_sum(float v, float *red) {
-    v = nz_wave_sum(v);
+    v = wave_sum(v);
     __syncthreads();                      // the previous use of red is over
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();

@@ -10,13 +10,9 @@
 //                        weight = scale * W * style  =>  sum_{i,t} weight^2 = sum_i wsq[o,i] s[b,i]^2)
 #include <algorithm>
 #include "g2s_common.h"
+#include "wave_sum.h"
 
 namespace g2s {
-
-__device__ __forceinline__ float wave_sum(float v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // one wavefront per row, 4 rows per workgroup.  Rows of any length: a scalar head brings the row
 // to 16-byte alignment (all operands share the row offset and have 16-byte aligned bases), then
@@ -64,13 +60,13 @@ __global__ __launch_bounds__(256) void rows_dot_scale(const float *__restrict__ 
     }
 }
 
-// one wavefront per (b, o)
-__global__ __launch_bounds__(256) void demod_fwd(const float *__restrict__ wsq,
-                                                 const float *__restrict__ s,
-                                                 float *__restrict__ demod, int B, int Cin, int Cout,
-                                                 float eps) {
-    const int idx = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (idx >= B * Cout) return;
+// The demodulation's arithmetic, once: the single-layer kernels (g2s_demod_fwd / _bwd / _bwd_add) and the kernels that
+// run every styled layer of the frozen generator in one launch (g2s_demod_*_multi) differ only in where the pointers
+// come from.
+// Forward, one wavefront per idx = (b, o).
+__device__ __forceinline__ void demod_fwd_one(const float *__restrict__ wsq, const float *__restrict__ s,
+                                              float *__restrict__ demod, int idx, int lane, int Cin, int Cout,
+                                              float eps) {
     const int b = idx / Cout, o = idx % Cout;
     const float *w = wsq + (size_t)o * Cin, *sb = s + (size_t)b * Cin;
     float acc = 0.0f;
@@ -79,17 +75,17 @@ __global__ __launch_bounds__(256) void demod_fwd(const float *__restrict__ wsq,
     if (lane == 0) demod[idx] = 1.0f / sqrtf(acc + eps);
 }
 
-// gs[b,i] = -s[b,i] * sum_o gd[b,o] * demod[b,o]^3 * wsq[o,i]
-// grid (ceil(Cin / 64), B); 4 waves split the o range, lanes run along i (coalesced wsq rows).
-__global__ __launch_bounds__(256) void demod_bwd(const float *__restrict__ wsq,
-                                                 const float *__restrict__ s,
-                                                 const float *__restrict__ demod,
-                                                 const float *__restrict__ gd,
-                                                 const float *gs_add,   // may alias gs (in-place add)
-                                                 float *gs, int B, int Cin, int Cout) {
+// Backward: g[b,i] = -s[b,i] * sum_o gd[b,o] * demod[b,o]^3 * wsq[o,i] for the 64 inputs i of one workgroup: 4 waves
+// split the o range, lanes run along i (coalesced wsq rows), the waves join through LDS.  The whole workgroup must
+// call it (it holds a barrier).  store(b * Cin + i, g) is the caller's: the single-layer entries write
+// `gs_add ? gs_add + g : g`, the multi-layer entry `gs += g`, which the compiler contracts with g's product into one
+// fused multiply-add — the two round differently, and each entry keeps its bits.
+template <typename Store>
+__device__ __forceinline__ void demod_bwd_one(const float *__restrict__ wsq, const float *__restrict__ s,
+                                              const float *__restrict__ demod, const float *__restrict__ gd, int i,
+                                              int b, int Cin, int Cout, Store store) {
     __shared__ float red[4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int i = blockIdx.x * 64 + lane, b = blockIdx.y;
     float acc = 0.0f;
     if (i < Cin) {
 #pragma unroll 8
@@ -102,8 +98,24 @@ __global__ __launch_bounds__(256) void demod_bwd(const float *__restrict__ wsq,
     __syncthreads();
     if (wave == 0 && i < Cin) {
         const float g = -s[b * Cin + i] * (red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane]);
-        gs[b * Cin + i] = gs_add ? gs_add[b * Cin + i] + g : g;
+        store(b * Cin + i, g);
     }
+}
+
+__global__ __launch_bounds__(256) void demod_fwd(const float *__restrict__ wsq, const float *__restrict__ s,
+                                                 float *__restrict__ demod, int B, int Cin, int Cout, float eps) {
+    const int idx = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (idx >= B * Cout) return;
+    demod_fwd_one(wsq, s, demod, idx, threadIdx.x & 63, Cin, Cout, eps);
+}
+
+// grid (ceil(Cin / 64), B)
+__global__ __launch_bounds__(256) void demod_bwd(const float *__restrict__ wsq, const float *__restrict__ s,
+                                                 const float *__restrict__ demod, const float *__restrict__ gd,
+                                                 const float *gs_add,   // may alias gs (in-place add)
+                                                 float *gs, int B, int Cin, int Cout) {
+    demod_bwd_one(wsq, s, demod, gd, blockIdx.x * 64 + (threadIdx.x & 63), blockIdx.y, Cin, Cout,
+                  [=](int at, float g) { gs[at] = gs_add ? gs_add[at] + g : g; });
 }
 
 // One pass over the activation x = gain * leaky_relu(yconv + noise_w * noise + bias) that sits between two layers of
@@ -117,26 +129,31 @@ __global__ __launch_bounds__(256) void demod_bwd(const float *__restrict__ wsq,
 //               (d loss / d demod of the producer; its convolution output is recovered from x: the leaky ReLU is
 //               invertible, so the forward never stores the pre-activation)
 // replacing four passes (rows_dot_scale x 2, the accumulation of the two consumers' gradients, the gate) by one.
-// One wavefront per row; every operand is read once.  PS (g2s_synth_bwd_rows_ps): one noise map per sample, noise
-// [rows / channels, n] — a row reads the map of b = row / channels, in gdot only; every sum keeps its order.
-template <bool PS>
+// One wavefront per row; every operand is read once.  noise_stride 0: one map [n] for the batch; n
+// (g2s_synth_bwd_rows_ps): one map per sample, noise [rows / channels, n] — a row reads the map of b = row / channels,
+// in gdot only; every sum keeps its order.
 __global__ __launch_bounds__(256) void synth_rows(const float *__restrict__ x, const float *__restrict__ g1,
                                                   const float *__restrict__ s1, const float *__restrict__ g2,
                                                   const float *__restrict__ s2, const float *__restrict__ noise,
                                                   const float *__restrict__ noise_w, const float *__restrict__ bias,
                                                   const float *__restrict__ demod, float *__restrict__ out,
                                                   float *__restrict__ dot1, float *__restrict__ dot2,
-                                                  float *__restrict__ gdot, int rows, int channels, int n, float slope,
-                                                  float gain, int vec) {
+                                                  float *__restrict__ gdot, int rows, int channels, int n,
+                                                  int noise_stride, float slope, float gain, int vec) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;
     const size_t off = (size_t)row * n;
     const float *xr = x + off, *g1r = g1 + off, *g2r = g2 ? g2 + off : nullptr;
     float *orow = out ? out + off : nullptr;
     const float a1 = s1[row], a2 = g2 ? s2[row] : 0.0f;
-    const float nw = gdot ? noise_w[0] : 0.0f, bi = gdot ? bias[row % channels] : 0.0f;
+    float nw = 0.0f, bi = 0.0f;
+    if (gdot) {
+        const int b = row / channels;          // one division: c = row - b * channels
+        nw = noise_w[0];
+        bi = bias[row - b * channels];
+        noise += (size_t)b * noise_stride;
+    }
     const float inv_gain = 1.0f / gain, inv_slope = 1.0f / slope;
-    if (PS && gdot) noise += (size_t)(row / channels) * n;
     float d1 = 0.0f, d2 = 0.0f, dg = 0.0f;
     auto one = [&](float xv, float gv1, float gv2, float nz) {
         d1 += xv * gv1;
@@ -203,40 +220,18 @@ struct DemodMulti {
 
 __global__ __launch_bounds__(256) void demod_fwd_multi(DemodMulti d) {
     const int l = blockIdx.y;
-    const int Cin = d.Cin[l], Cout = d.Cout[l];
-    const int idx = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (idx >= d.B * Cout) return;
-    const int b = idx / Cout, o = idx % Cout;
-    const float *w = d.wsq[l] + (size_t)o * Cin, *sb = d.s[l] + (size_t)b * Cin;
-    float acc = 0.0f;
-    for (int i = lane; i < Cin; i += 64) acc += w[i] * sb[i] * sb[i];
-    acc = wave_sum(acc);
-    if (lane == 0) d.demod[l][idx] = 1.0f / sqrtf(acc + d.eps);
+    const int idx = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (idx >= d.B * d.Cout[l]) return;
+    demod_fwd_one(d.wsq[l], d.s[l], d.demod[l], idx, threadIdx.x & 63, d.Cin[l], d.Cout[l], d.eps);
 }
 
 // grid (ceil(max Cin / 64), B, layers): demod_bwd of every layer, added in place to gs (the convolution path's sum)
 __global__ __launch_bounds__(256) void demod_bwd_multi(DemodMulti d) {
-    __shared__ float red[4][64];
     const int l = blockIdx.z;
-    const int Cin = d.Cin[l], Cout = d.Cout[l];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int i = blockIdx.x * 64 + lane, b = blockIdx.y;
-    if (blockIdx.x * 64 >= Cin) return;      // whole workgroup: no barrier is skipped by part of it
-    const float *wsq = d.wsq[l], *demod = d.demod[l], *gd = d.gd[l];
-    float acc = 0.0f;
-    if (i < Cin) {
-#pragma unroll 8
-        for (int o = wave; o < Cout; o += 4) {
-            const float dm = demod[b * Cout + o];
-            acc += gd[b * Cout + o] * dm * dm * dm * wsq[(size_t)o * Cin + i];
-        }
-    }
-    red[wave][lane] = acc;
-    __syncthreads();
-    if (wave == 0 && i < Cin) {
-        const float g = -d.s[l][b * Cin + i] * (red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane]);
-        d.gs[l][b * Cin + i] += g;
-    }
+    if (blockIdx.x * 64 >= d.Cin[l]) return;      // whole workgroup: no barrier is skipped by part of it
+    float *gs = d.gs[l];
+    demod_bwd_one(d.wsq[l], d.s[l], d.demod[l], d.gd[l], blockIdx.x * 64 + (threadIdx.x & 63), blockIdx.y, d.Cin[l],
+                  d.Cout[l], [=](int at, float g) { gs[at] += g; });
 }
 
 }  // namespace g2s
@@ -295,37 +290,39 @@ extern "C" int g2s_channel_sum(const float *g, float *out, int B, int C, int n, 
     return check_launch("g2s_channel_sum");
 }
 
-template <bool PS>
-static int synth_bwd_rows_launch(const float *x, const float *g1, const float *s1, const float *g2, const float *s2,
-                                 const float *noise, const float *noise_w, const float *bias, const float *demod,
-                                 float *out, float *dot1, float *dot2, float *gdot, int rows, int channels, int n,
-                                 float slope, float gain, g2s_stream_t stream) {
+static int synth_bwd_rows_launch(const char *who, int noise_stride, const float *x, const float *g1, const float *s1,
+                                 const float *g2, const float *s2, const float *noise, const float *noise_w,
+                                 const float *bias, const float *demod, float *out, float *dot1, float *dot2,
+                                 float *gdot, int rows, int channels, int n, float slope, float gain,
+                                 g2s_stream_t stream) {
     G2S_REQUIRE(x && g1 && s1 && dot1 && rows > 0 && channels > 0 && n > 0, "x, g1, s1, dot1 must not be NULL; sizes positive");
     G2S_REQUIRE((g2 == nullptr) == (s2 == nullptr) && (g2 == nullptr) == (dot2 == nullptr), "g2, s2, dot2 come together");
     G2S_REQUIRE(!gdot || (noise && noise_w && bias && demod), "gdot needs noise, noise_w, bias, demod");
     G2S_REQUIRE(slope > 0.0f && gain > 0.0f, "slope and gain must be positive (the activation is inverted)");
     uintptr_t bits = (uintptr_t)x | (uintptr_t)g1 | (uintptr_t)g2 | (uintptr_t)out | (gdot ? (uintptr_t)noise : 0);
     const int vec = (n % 4 == 0) && (bits & 15) == 0;
-    if (PS) G2S_REQUIRE(rows % channels == 0, "rows must be a multiple of channels with one noise map per sample");
-    synth_rows<PS><<<cdiv(rows, 4), 256, 0, as_stream(stream)>>>(x, g1, s1, g2, s2, noise, noise_w, bias, demod, out,
-                                                                   dot1, dot2, gdot, rows, channels, n, slope, gain, vec);
-    return check_launch(PS ? "g2s_synth_bwd_rows_ps" : "g2s_synth_bwd_rows");
+    if (noise_stride)
+        G2S_REQUIRE(rows % channels == 0, "rows must be a multiple of channels with one noise map per sample");
+    synth_rows<<<cdiv(rows, 4), 256, 0, as_stream(stream)>>>(x, g1, s1, g2, s2, noise, noise_w, bias, demod, out, dot1,
+                                                               dot2, gdot, rows, channels, n, noise_stride, slope, gain,
+                                                               vec);
+    return check_launch(who);
 }
 
 extern "C" int g2s_synth_bwd_rows(const float *x, const float *g1, const float *s1, const float *g2, const float *s2,
                                   const float *noise, const float *noise_w, const float *bias, const float *demod,
                                   float *out, float *dot1, float *dot2, float *gdot, int rows, int channels, int n,
                                   float slope, float gain, g2s_stream_t stream) {
-    return synth_bwd_rows_launch<false>(x, g1, s1, g2, s2, noise, noise_w, bias, demod, out, dot1, dot2, gdot, rows,
-                                        channels, n, slope, gain, stream);
+    return synth_bwd_rows_launch("g2s_synth_bwd_rows", 0, x, g1, s1, g2, s2, noise, noise_w, bias, demod, out, dot1,
+                                 dot2, gdot, rows, channels, n, slope, gain, stream);
 }
 
 extern "C" int g2s_synth_bwd_rows_ps(const float *x, const float *g1, const float *s1, const float *g2, const float *s2,
                                      const float *noise, const float *noise_w, const float *bias, const float *demod,
                                      float *out, float *dot1, float *dot2, float *gdot, int rows, int channels, int n,
                                      float slope, float gain, g2s_stream_t stream) {
-    return synth_bwd_rows_launch<true>(x, g1, s1, g2, s2, noise, noise_w, bias, demod, out, dot1, dot2, gdot, rows,
-                                       channels, n, slope, gain, stream);
+    return synth_bwd_rows_launch("g2s_synth_bwd_rows_ps", n, x, g1, s1, g2, s2, noise, noise_w, bias, demod, out, dot1,
+                                 dot2, gdot, rows, channels, n, slope, gain, stream);
 }
 
 extern "C" int g2s_rows_dot_scale(const float *a, const float *b, const float *s, const float *inv,

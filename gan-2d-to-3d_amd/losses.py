@@ -68,8 +68,6 @@ class _DFeatureL1(torch.autograd.Function):
               and the residual join (a + b) / sqrt(2) as one launch.
     Same arithmetic as DiscriminatorLoss.__call__'s op-by-op form below."""
 
-    FUSED_LEVELS = True        # join + masked-L1 gradient + conv2's gate as one launch per level (g2s_weighted_l1_bwd3)
-
     @staticmethod
     def forward(ctx, fake, real, D, count, weights):
         from . import lib as _lib
@@ -103,7 +101,6 @@ class _DFeatureL1(torch.autograd.Function):
     def backward(ctx, g_total):
         from . import lib as _lib
         from .modconv import DOWN2, PLAIN, modconv_raw, relu_gate
-        from .op import add_bias_scale
         from .op.upfirdn2d import upfirdn2d_adjoint
         L = _lib.load()
         N = ctx.N
@@ -126,15 +123,7 @@ class _DFeatureL1(torch.autograd.Function):
         add = None          # (gx_main, gx_skip) of the block above: joined inside the next level's launch
         for level in range(len(ctx.blocks) - 1, -1, -1):
             blk, in_hw, y1, y2, feat, wc = ctx.blocks[level]
-            if _DFeatureL1.FUSED_LEVELS:
-                g, g2 = level_grad(feat, wc, ctx.numden[level, 1:], add, y2[:N])
-            else:
-                joined = None if add is None else add_bias_scale(add[0], add[1], None, 2 ** -0.5)
-                g = torch.empty(y2[:N].shape, dtype=torch.float32, device=feat.device)
-                _lib.check(L.g2s_weighted_l1_bwd2(_lib.ptr(feat[:N]), _lib.ptr(feat[N:]), _lib.ptr(wc), _lib.ptr(g_total),
-                                                  _lib.ptr(ctx.numden[level, 1:]), _lib.ptr(joined), _lib.ptr(g), N,
-                                                  feat.shape[1], feat.shape[2] * feat.shape[3], _lib.stream()))
-                g2 = relu_gate(g, y2[:N], slope, gain)
+            g, g2 = level_grad(feat, wc, ctx.numden[level, 1:], add, y2[:N])
             # out = (conv2(conv1(x)) + skip(x)) / sqrt(2): both branches keep the common factor, the join applies it
             conv2, conv1, skip = blk.conv2, blk.conv1, blk.skip
             w2 = conv2[-2]._w.get(conv2[-2].weight, conv2[-2].scale)
@@ -153,10 +142,7 @@ class _DFeatureL1(torch.autograd.Function):
             add = (gx_main, gx_skip)
         first = ctx.first
         w0 = first[-2]._w.get(first[-2].weight, first[-2].scale)
-        if _DFeatureL1.FUSED_LEVELS:
-            _, g0 = level_grad(None, None, None, add, ctx.y0[:N].contiguous())      # the last join + the first layer's gate
-        else:
-            g0 = relu_gate(add_bias_scale(add[0], add[1], None, 2 ** -0.5), ctx.y0[:N], slope, gain)
+        _, g0 = level_grad(None, None, None, add, ctx.y0[:N].contiguous())      # the last join + the first layer's gate
         gx = modconv_raw(g0, w0, None, None, PLAIN, 1)
         return gx, None, None, None, None
 

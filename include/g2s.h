@@ -645,8 +645,9 @@ int g2s_synth_bwd_rows(const float *x, const float *g1, const float *s1, const f
                        float *dot1, float *dot2, float *gdot, int rows, int channels, int n, float slope, float gain,
                        g2s_stream_t stream);
 /* g2s_synth_bwd_rows with ONE MAP PER SAMPLE: noise [B = rows / channels, n] (rows a multiple of channels); row r reads
- * the map of b = r / channels, in gdot only.  The same kernel body: every sum keeps its order, no atomics, the same
- * bits in either mode of g2s_set_deterministic, and B equal maps give g2s_synth_bwd_rows' bits. */
+ * the map of b = r / channels, in gdot only.  The same kernel with a noise stride of n instead of 0: every sum keeps its
+ * order, no atomics, the same bits in either mode of g2s_set_deterministic, and B equal maps give g2s_synth_bwd_rows'
+ * bits. */
 int g2s_synth_bwd_rows_ps(const float *x, const float *g1, const float *s1, const float *g2, const float *s2,
                           const float *noise, const float *noise_w, const float *bias, const float *demod, float *out,
                           float *dot1, float *dot2, float *gdot, int rows, int channels, int n, float slope, float gain,
@@ -728,7 +729,9 @@ int g2s_weighted_l1_bwd2(const float *x, const float *y, const float *w, const f
 /* One launch per level of the discriminator-feature loss's backward (losses._DFeatureL1; GAN2Shape/losses.py:11-36 on
  * stylegan2-pytorch/model.py:679-697):  gx = (gadd + gadd2) * add_scale + [x != NULL] sign(x - y) w g[0] / den[0] — the
  * residual join of the block above with this level's masked-L1 gradient — and, optionally, gx_gate = gx * gain *
- * (gate_ref > 0 ? 1 : slope), the gradient behind the block's activated conv2.  Any of gadd2, gx, gx_gate may be NULL. */
+ * (gate_ref > 0 ? 1 : slope), the gradient behind the block's activated conv2.  Any of gadd2, gx, gx_gate may be NULL.
+ * _bwd and _bwd2 are launches of the same kernel (den = NULL; gadd2 = NULL, add_scale = 1, no gate): where their
+ * arguments describe the same sum, the three entries give the same bits. */
 int g2s_weighted_l1_bwd3(const float *x, const float *y, const float *w, const float *g, const float *den,
                          const float *gadd, const float *gadd2, float add_scale, float *gx, const float *gate_ref,
                          float slope, float gain, float *gx_gate, int B, int C, int HW, g2s_stream_t stream);
