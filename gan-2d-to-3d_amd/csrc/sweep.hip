@@ -17,6 +17,17 @@
 //                           vertices from the maps of image b = f / V (a few hundred KB, resident in L2 for all V
 //                           frames), then the mode's colour; flip + ssaa x ssaa average and alpha as
 //                           g2s_raster_rgba_fwd.  No atomics: bit-identical from run to run.
+//
+// The pseudo-view path (Renderer.render_pseudo_sweep) shares the first two launches and ends in
+//   sweep_pseudo_kernel     the inverse-warp renderer the offset encoder was trained on (render_given_view with
+//                           grid_sample=True after the relighting of sample_pseudo_imgs) for B*V frames at once: per
+//                           output pixel the clamp of warp_canon_depth, the inverse of the frame's pose, K, the
+//                           bilinear read of the RELIT canonical image and the nearest read of the canonical mask.
+//                           The relit image is never formed: the four taps are shaded from the albedo and the normals
+//                           of image b = f / V (6 S^2 floats, resident in L2 for all V frames) and then interpolated,
+//                           which is "shade, then grid_sample" tap for tap.  One thread per output pixel, a workgroup
+//                           lies inside one frame, so pose and light are wave-uniform loads; gather- and latency-
+//                           bound, the stores are coalesced rows of a plane.  No atomics.
 // No backward: nothing here carries a gradient.
 #include "g2s_common.h"
 #include "raster_core.h"
@@ -189,6 +200,94 @@ static void launch_shade(const ShadeParams &p, int mode, hipStream_t st) {
     else sweep_shade_kernel<IMPLICIT, 3><<<blocks, 256, 0, st>>>(p);
 }
 
+
+struct PseudoParams {
+    const float *warped;     // [B*V, P] rasterised depth of the posed meshes, unclamped
+    const float *rays;       // [P, 3]
+    const float *pose;       // [B, V, 12]
+    const float *albedo;     // [B, C, P]
+    const float *normal;     // [B, P, 3] or NULL
+    const float *light;      // [B*V, 4] or NULL
+    const float *mask;       // [B, P] or NULL
+    float *im;               // [B*V, C, P]
+    float *mask_out;         // [B*V, P] or NULL
+    int V, S, C, bpf;        // bpf = workgroups per frame
+    float lo, hi;
+    float k00, k01, k02, k10, k11, k12;
+};
+
+__global__ __launch_bounds__(256) void sweep_pseudo_kernel(PseudoParams a) {
+    const int f = blockIdx.x / a.bpf;                       // wave-uniform: frame, image, pose and light
+    const int p = (blockIdx.x - f * a.bpf) * 256 + threadIdx.x;
+    const int S = a.S, P = S * S;
+    if (p >= P) return;
+    const int b = f / a.V;
+    const float *q = a.pose + (size_t)f * 12;
+    float d = a.warped[(size_t)f * P + p];
+    d = d < a.lo ? a.lo : (d > a.hi ? a.hi : d);
+    // q = A^T (d ray - t), the inverse of the posed-vertex map, in double: t = c + t_view - R c has the size of the
+    // rotation centre's depth and d ray - t cancels most of it, so in float the texel coordinate would carry several
+    // times the rounding of the composed route (which subtracts c first).  A few dozen fp64 operations per pixel of a
+    // gather-bound pass.  The normalisation of grid_3d_to_2d and the un-normalisation of grid_sample
+    // (align_corners = True) cancel: K q / q.z IS the texel coordinate.
+    const double zx = (double)a.rays[3 * p] * d - q[9], zy = (double)a.rays[3 * p + 1] * d - q[10],
+                 zz = (double)a.rays[3 * p + 2] * d - q[11];
+    const double yx = (zx * q[0] + zy * q[3]) + zz * q[6];
+    const double yy = (zx * q[1] + zy * q[4]) + zz * q[7];
+    const double yz = (zx * q[2] + zy * q[5]) + zz * q[8];
+    const double pa = yx / yz, pb = yy / yz;
+    const float ix = (float)((pa * a.k00 + pb * a.k01) + a.k02), iy = (float)((pa * a.k10 + pb * a.k11) + a.k12);
+    const float fx = floorf(ix), fy = floorf(iy);
+    // a float outside the int range (or NaN) must not hit undefined conversion: such a pixel has no tap in range
+    const bool sane = fx >= -2.0f && fx <= (float)S && fy >= -2.0f && fy <= (float)S;
+    const int x0 = sane ? (int)fx : -2, y0 = sane ? (int)fy : -2;
+    const float wx0 = (fx + 1.0f) - ix, wx1 = ix - fx, wy0 = (fy + 1.0f) - iy, wy1 = iy - fy;
+    const float w[4] = {wx0 * wy0, wx1 * wy0, wx0 * wy1, wx1 * wy1};          // nw, ne, sw, se
+    bool in[4];
+    int at[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int x = x0 + (k & 1), y = y0 + (k >> 1);
+        in[k] = x >= 0 && x < S && y >= 0 && y < S;
+        at[k] = in[k] ? y * S + x : 0;                                          // only dereferenced when in range
+    }
+    float sh[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+    if (a.light) {
+        const float *l = a.light + (size_t)f * 4;
+        const float la = l[0] / 2.0f + 0.5f, lb = l[1] / 2.0f + 0.5f;
+        const float nrm = sqrtf(l[2] * l[2] + l[3] * l[3] + 1.0f);
+        const float dx = l[2] / nrm, dy = l[3] / nrm, dz = 1.0f / nrm;
+        const float *nb = a.normal + (size_t)b * P * 3;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (!in[k]) continue;
+            const float *n = nb + (size_t)at[k] * 3;
+            const float dot = n[0] * dx + n[1] * dy + n[2] * dz;
+            sh[k] = la + lb * (dot > 0.0f ? dot : 0.0f);
+        }
+    }
+    const float *al = a.albedo + (size_t)b * a.C * P;
+    float *o = a.im + (size_t)f * a.C * P + p;
+    for (int c = 0; c < a.C; c++, al += P, o += P) {
+        float v = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (!in[k]) continue;
+            const float t = a.light ? (al[at[k]] / 2.0f + 0.5f) * sh[k] * 2.0f - 1.0f : al[at[k]];
+            v += t * w[k];
+        }
+        *o = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);     // NaN passes through, like torch.clamp
+    }
+    if (a.mask_out) {
+        // mode='nearest': round half to even, zero padding
+        const float rx = rintf(ix), ry = rintf(iy);
+        const bool inside = rx >= 0.0f && rx <= (float)(S - 1) && ry >= 0.0f && ry <= (float)(S - 1);
+        float m = 0.0f;
+        if (inside) m = a.mask ? a.mask[(size_t)b * P + (int)ry * S + (int)rx] : 1.0f;
+        a.mask_out[(size_t)f * P + p] = m;
+    }
+}
+
 }  // namespace g2s
 
 using namespace g2s;
@@ -249,4 +348,41 @@ extern "C" int g2s_sweep_shade(const float *verts, const int32_t *faces, const i
     if (faces) launch_shade<false>(p, mode, as_stream(stream));
     else launch_shade<true>(p, mode, as_stream(stream));
     return check_launch("g2s_sweep_shade");
+}
+
+extern "C" int g2s_sweep_pseudo(const float *warped, const float *rays, const float *pose, const float *K,
+                                const float *albedo, const float *normal, const float *light, const float *mask,
+                                float depth_lo, float depth_hi, int B, int V, int S, int C, float *im_out,
+                                float *mask_out, g2s_stream_t stream) {
+    G2S_REQUIRE(warped && rays && pose && K && albedo && im_out, "g2s_sweep_pseudo: NULL pointer argument");
+    G2S_REQUIRE(B > 0 && V > 0, "g2s_sweep_pseudo: sizes must be positive");
+    G2S_REQUIRE(S >= 2 && S <= 16384, "g2s_sweep_pseudo: S = %d outside 2..16384", S);
+    G2S_REQUIRE(C >= 1 && C <= 4, "g2s_sweep_pseudo: C = %d outside 1..4", C);
+    G2S_REQUIRE((normal == nullptr) == (light == nullptr),
+                "g2s_sweep_pseudo: normal and light go together (both, or neither for no relighting)");
+    G2S_REQUIRE(depth_lo <= depth_hi, "g2s_sweep_pseudo: depth_lo > depth_hi");
+    const long bpf = cdiv((long)S * S, 256);
+    // HIP launches at most 2^32 - 1 threads per grid dimension: 256 threads x fewer than 2^24 workgroups
+    G2S_REQUIRE((long)B * V * bpf < (1L << 24), "g2s_sweep_pseudo: B * V * ceil(S*S / 256) = %ld workgroups exceed the grid (2^24)",
+                (long)B * V * bpf);
+    PseudoParams a{};
+    a.warped = warped;
+    a.rays = rays;
+    a.pose = pose;
+    a.albedo = albedo;
+    a.normal = normal;
+    a.light = light;
+    a.mask = mask;
+    a.im = im_out;
+    a.mask_out = mask_out;
+    a.V = V;
+    a.S = S;
+    a.C = C;
+    a.bpf = (int)bpf;
+    a.lo = depth_lo;
+    a.hi = depth_hi;
+    a.k00 = K[0]; a.k01 = K[1]; a.k02 = K[2];
+    a.k10 = K[3]; a.k11 = K[4]; a.k12 = K[5];
+    sweep_pseudo_kernel<<<(unsigned)((long)B * V * bpf), 256, 0, as_stream(stream)>>>(a);
+    return check_launch("g2s_sweep_pseudo");
 }

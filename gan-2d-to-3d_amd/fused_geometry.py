@@ -181,6 +181,8 @@ class ShadingFunction(Function):
         B = light.shape[0]
         Bn, H, W, _ = normal.shape
         Ba = albedo.shape[0]
+        if albedo.dim() != 4 or albedo.shape[1] != 3:      # the kernel reads three planes per image
+            raise ValueError(f"shading: albedo must be [Ba, 3, H, W], got {tuple(albedo.shape)}")
         diffuse = torch.empty((B, 1, H, W), dtype=torch.float32, device=light.device)
         texture = torch.empty((B, 3, H, W), dtype=torch.float32, device=light.device)
         L = _lib.load()

@@ -46,6 +46,7 @@ SIGNATURES = {
     "g2s_raster_rgba_bwd": (_i, [_p] * 7 + [_i, _i, _i, _i, _p, _f, _i, _i, _i, _i, _f, _p, _p, _p, _p, _sz, _i, _p]),
     "g2s_sweep_verts": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "g2s_sweep_shade": (_i, [_p] * 8 + [_i] * 9 + [_p, _f, _p, _p, _p]),
+    "g2s_sweep_pseudo": (_i, [_p] * 8 + [_f, _f, _i, _i, _i, _i, _p, _p, _p]),
     "g2s_mapping_tile": (_i, []),
     "g2s_mapping_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _f, _f, _f, _p]),
     "g2s_rows_mean": (_i, [_p, _p, _i64, _i, _i64, _p]),

@@ -437,6 +437,69 @@ class GAN2Shape(nn.Module):
         mask = mask[:, 0, None, ...]
         return pseudo_im.clamp(min=-1, max=1), mask.contiguous()
 
+    # ------------------------------------------------------------------ manipulation through the GAN
+    def decompose(self, image):
+        """The head of forward_step1 without its losses, under no_grad: the four nets on `image` (1,3,S,S) ->
+        dict(collected=(normal, light_a, light_b, albedo, depth, canon_mask) as forward_step1 returns it, view (1,6)
+        and light (1,4): the predicted view and lighting with the sampler's means added, as the nets give them).
+        forward_step1 itself is not called: it would run the losses and begin a training step's pool, and it does
+        not hand out the raw view and lighting.  This is therefore a second statement of its head (each net called
+        on its own, not through the paired or forked routes, which differ in rounding only) and HAS TO FOLLOW any
+        change made there; tests/test_gpu_manipulate.py holds the two to each other."""
+        with torch.no_grad():
+            h = w = self.image_size
+            depth = self.get_clamped_depth(self.depth_net(image).squeeze(1), h, w)
+            albedo = self.albedo_net(image)
+            view = self.viewpoint_net(image) + self.view_light_sampler.view_mean.unsqueeze(0)
+            light = self.lighting_net(image) + self.view_light_sampler.light_mean.unsqueeze(0)
+            normal = self.renderer.get_normal_from_depth(depth)
+            ab = light[:, :2] / 2 + 0.5
+        return dict(collected=(normal, ab[:, :1], ab[:, 1:2], albedo, depth, None), view=view, light=light)
+
+    def manipulate(self, image, latent, views, lights=None, relative=False, gan_batch=8):
+        """3D-aware manipulation through the GAN: the recovered shape of `image` (1,3,S,S) rotated and relit, every
+        frame pushed through the offset encoder and the frozen generator, as the forward half of step 2 does for
+        its random draws.  latent: the image's w (style_dim,) or (1,style_dim).  views (V,6): one pose per frame in
+        the units `renderer.set_transform_matrices` takes (radians, translations; `rotation_views`), about the
+        canonical frame, or composed after the predicted view when `relative` (zeros = the input's own pose).
+        lights (V,4): raw (a, b, dx, dy) rows as the lighting net gives them (`light_sweep`), None = the predicted
+        light on every frame.  The generator runs `gan_batch` frames at a time with its fixed noise buffers.
+        Under no_grad.  Returns dict(pseudo (V,3,S,S) the rendered frames, mask (V,1,S,S), gan (V,3,S,S) the GAN's
+        images resized to image_size, w (V,style_dim) = latent + offset, view (1,6), light (1,4) the predictions)."""
+        F1_d = 2
+        gan_batch = int(gan_batch)
+        if gan_batch < 1:
+            raise ValueError("gan_batch must be at least 1")
+        if image.dim() != 4 or image.shape[0] != 1:
+            raise ValueError(f"manipulate takes one image (1,3,S,S), got {tuple(image.shape)}")
+        with torch.no_grad():
+            latent = latent.to(self.device).reshape(1, -1)
+            views = torch.as_tensor(views, dtype=torch.float32, device=self.device)
+            if views.dim() != 2 or views.shape[1] != 6:
+                raise ValueError(f"views must be (V, 6), got {tuple(views.shape)}")
+            V = views.shape[0]
+            d = self.decompose(image)
+            normal, _, _, albedo, depth, canon_mask = d["collected"]
+            if lights is None:
+                lights = d["light"].expand(V, 4)
+            base = self.get_view_transformation(d["view"]) if relative else None
+            pseudo, mask = self.renderer.render_pseudo_sweep(albedo, normal, depth, views, lights, canon_mask,
+                                                             base_view=base)
+            pseudo, mask = pseudo[0], mask[0]
+            gan_im = None
+            if self.relative_encoding:
+                gan_im, _ = self.generator([latent], input_is_w=True, truncation_latent=self.mean_latent,
+                                           truncation=self.truncation, randomize_noise=False)
+                gan_im = utils.resize(gan_im.clamp(min=-1, max=1), [self.image_size, self.image_size])
+            center_w, center_h = self._latent_centers()
+            offset, w = self.latent_projection(pseudo, gan_im, latent, center_w, center_h, F1_d)
+            frames = []
+            for i in range(0, V, gan_batch):
+                j = slice(i, i + gan_batch)
+                projected, _ = self.generator.invert(pseudo[j], (offset[j], w[j]), self.truncation, self.mean_latent)
+                frames.append(utils.resize(projected, [self.image_size, self.image_size]))
+        return dict(pseudo=pseudo, mask=mask, gan=torch.cat(frames, 0), w=w, view=d["view"], light=d["light"])
+
     # ------------------------------------------------------------------ step 3
     def forward_step3(self, images, latents, collected, **kwargs):
         """model.py:225-280: optimise V, L, D, A on the image and its projected samples."""
@@ -569,6 +632,25 @@ class GAN2Shape(nn.Module):
             if not general:
                 img_ids.append(int(words[words.index('image') + 1]))
         return paths, img_ids
+
+
+def rotation_views(yaw_max_deg, frames, pitch_deg=0):
+    """(frames, 6) views for GAN2Shape.manipulate: the yaw runs evenly from -yaw_max_deg to +yaw_max_deg at the constant
+    pitch `pitch_deg`, no roll and no translation; angles in radians, (rx, ry, rz, tx, ty, tz) as
+    get_transform_matrices takes them (rx = pitch, ry = yaw)."""
+    views = torch.zeros(int(frames), 6)
+    views[:, 0] = math.pi / 180 * pitch_deg
+    views[:, 1] = torch.linspace(-math.pi / 180 * yaw_max_deg, math.pi / 180 * yaw_max_deg, int(frames))
+    return views
+
+
+def light_sweep(light_a, light_b, frames, radius):
+    """(frames, 4) raw light rows (a, b, dx, dy) for GAN2Shape.manipulate: ambient and diffuse terms as given (raw:
+    the shading uses a / 2 + 0.5 and b / 2 + 0.5), and (dx, dy) = radius (cos phi_i, sin phi_i), phi_i = 2 pi i /
+    frames, once round a circle; the direction is (dx, dy, 1) normalised."""
+    phi = torch.arange(int(frames), dtype=torch.float64) * (2 * math.pi / int(frames))
+    ab = torch.tensor([float(light_a), float(light_b)], dtype=torch.float64).expand(int(frames), 2)
+    return torch.cat([ab, radius * phi.cos()[:, None], radius * phi.sin()[:, None]], 1).float()
 
 
 class ViewLightSampler():

@@ -615,6 +615,66 @@ def sweep_frames(verts, pose, faces, attr, normal, light, K, orig_size, image_si
     return rgb, alpha, depth.view(B, V, S, S) if want_depth else None
 
 
+def pseudo_frames(verts, pose, rays, K, albedo, normal, light, mask, depth_lo, depth_hi, orig_size, image_size,
+                  anti_aliasing, fill_back, want_mask=True):
+    """The three launches of the pseudo-view path, without autograd (there is no backward): g2s_sweep_verts,
+    g2s_raster_depth_fwd over the B*V posed meshes with render_depth's near / far and no saved maps, g2s_sweep_pseudo
+    (include/g2s.h).  verts (B,S*S,3), pose (B,V,12), rays (S*S,3), albedo (B,C,S,S), normal (B,S,S,3) and light
+    (B*V,4) both or neither, mask (B,S,S) or None.  Every shape is checked before the first launch.  Returns
+    (im (B,V,C,S,S), mask (B,V,S,S) or None)."""
+    S = int(image_size)
+    B, V = check_pseudo_shapes(verts.shape, pose.shape, rays.shape, albedo.shape, None if normal is None else normal.shape,
+                               None if light is None else light.shape, None if mask is None else mask.shape, S)
+    _lib.require_cuda(verts, pose, rays, albedo, normal, light, mask)
+    with torch.no_grad():
+        verts, pose, rays, albedo = (t.float().contiguous() for t in (verts, pose, rays, albedo))
+        normal, light, mask = (None if t is None else t.float().contiguous() for t in (normal, light, mask))
+        C, N = albedo.shape[1], S * S
+        ssaa = 2 if anti_aliasing else 1
+        F = 2 * (S - 1) * (S - 1)
+        L = _lib.load()
+        st = _lib.stream()
+        dev = verts.device
+        posed = torch.empty((B * V, N, 3), dtype=torch.float32, device=dev)
+        _lib.check(L.g2s_sweep_verts(_lib.ptr(verts), _lib.ptr(pose), _lib.ptr(posed), B, V, N, st))
+        warped = torch.empty((B * V, S, S), dtype=torch.float32, device=dev)
+        ws = _workspace(dev, L.g2s_raster_workspace_bytes(B * V, N, F, S))
+        Kc = (_lib.C.c_float * 9)(*K)
+        _lib.check(L.g2s_raster_depth_fwd(_lib.ptr(posed), None, B * V, N, F, S, Kc, float(orig_size), ssaa,
+                                          int(bool(fill_back)), DEFAULT_NEAR, DEFAULT_FAR, _lib.ptr(warped), None, None,
+                                          _lib.ptr(ws), ws.numel(), st))
+        im = torch.empty((B, V, C, S, S), dtype=torch.float32, device=dev)
+        mout = torch.empty((B, V, S, S), dtype=torch.float32, device=dev) if want_mask else None
+        _lib.check(L.g2s_sweep_pseudo(_lib.ptr(warped), _lib.ptr(rays), _lib.ptr(pose), Kc, _lib.ptr(albedo),
+                                      _lib.ptr(normal), _lib.ptr(light), _lib.ptr(mask), float(depth_lo),
+                                      float(depth_hi), B, V, S, C, _lib.ptr(im), _lib.ptr(mout), st))
+    return im, mout
+
+
+def check_pseudo_shapes(verts, pose, rays, albedo, normal, light, mask, S):
+    """The argument checks of `pseudo_frames` on plain shapes (no device needed) -> (B, V); ValueError otherwise."""
+    verts, pose, rays, albedo = tuple(verts), tuple(pose), tuple(rays), tuple(albedo)
+    B = verts[0]
+    if S < 2 or verts != (B, S * S, 3):
+        raise ValueError(f"verts must be [B, S*S = {S * S}, 3] with S >= 2, got {verts}")
+    if len(pose) != 3 or pose[0] != B or pose[2] != 12 or pose[1] < 1:
+        raise ValueError(f"pose must be [B={B}, V, 12], got {pose}")
+    V = pose[1]
+    if rays != (S * S, 3):
+        raise ValueError(f"rays must be [S*S = {S * S}, 3], got {rays}")
+    if len(albedo) != 4 or albedo[0] != B or not 1 <= albedo[1] <= 4 or albedo[2:] != (S, S):
+        raise ValueError(f"albedo must be [B={B}, C in 1..4, {S}, {S}], got {albedo}")
+    if (normal is None) != (light is None):
+        raise ValueError("normal and light go together: both, or neither for no relighting")
+    if normal is not None and tuple(normal) != (B, S, S, 3):
+        raise ValueError(f"normal must be [B={B}, {S}, {S}, 3], got {tuple(normal)}")
+    if light is not None and tuple(light) != (B * V, 4):
+        raise ValueError(f"light must be [B*V = {B * V}, 4] rows of (a, b, dx, dy), got {tuple(light)}")
+    if mask is not None and tuple(mask) != (B, S, S):
+        raise ValueError(f"mask must be [B={B}, {S}, {S}], got {tuple(mask)}")
+    return B, V
+
+
 def sweep_shade_torch(verts, faces, face_idx, bary, attr, normal, pose, light, B, V, S, ssaa, fill_back, mode,
                       background, grey=0.7):
     """g2s_sweep_shade (include/g2s.h) written in torch ops, on any device and in the dtype of `verts`: the float32

@@ -11,7 +11,9 @@ rasterizer (`render_rgb`); their pose sweeps share one helper (`_sweep`).  That 
 differentiable: everything around `render_rgb` is torch ops, so render_given_view(im, depth, view,
 grid_sample=False) carries gradients to `im`, `depth` and `view` (gradient of the texture lookup,
 no silhouette term — plugins/neural_renderer.py).  render_sweep is the batched viewing path beside them (no gradient):
-all poses of a sweep in three launches (csrc/sweep.hip).
+all poses of a sweep in three launches (csrc/sweep.hip).  render_pseudo_sweep is the batched form of the training
+renderer itself (relight + render_given_view(grid_sample=True)), for manipulation through the GAN: also three
+launches, no gradient.
 """
 import math
 
@@ -319,14 +321,7 @@ class Renderer():
                 faces = r._shared_faces(faces, h * w, S)
             bg = r.background_color if background is None else background
             ssaa = 2 if r.anti_aliasing else 1
-            if max_frames is None:
-                per_frame = (S * ssaa) ** 2 * 16 + h * w * 12
-                max_frames = max(1, (256 << 20) // per_frame)
-            max_frames = int(max_frames)
-            if max_frames < 1:
-                raise ValueError("max_frames must be at least 1")
-            bc = min(b, max_frames)
-            vc = min(V, max(1, max_frames // bc))
+            bc, vc = sweep_chunks(b, V, max_frames, (S * ssaa) ** 2 * 16 + h * w * 12)
             K = r._host_K(r.K)
             out = alpha = dmap = None
             for b0 in range(0, b, bc):
@@ -351,6 +346,93 @@ class Renderer():
         result = (out,) + ((alpha,) if return_alpha else ()) + ((dmap,) if return_depth else ())
         return result[0] if len(result) == 1 else result
 
+    def pseudo_pose(self, views, base_view=None, b=1):
+        """(b, V, 12) = row-major A, then t, of the posed-vertex map of `get_warped_3d_grid` for every frame: with c
+        the rotation centre and (R, t_view) the view's transform, p -> R (p - c) + c + t_view, so A = R and
+        t = c + t_view - R c (`compose_sweep_pose` with the view's translation as its `v_after`, written out: a handful
+        of small products on the device, no host synchronisation).  base_view (b,6): each frame's view is applied
+        AFTER it, A = R R0 and t = c + t_view + R t0 - A c.  views: (V,6) or (b,V,6)."""
+        if views.dim() == 2:
+            views = views.unsqueeze(0).expand(b, -1, -1)
+        V = views.shape[1]
+
+        def transform(v):
+            v = v.contiguous()
+            return fg.view_transform(v) if self._use_fused(v) else get_transform_matrices(v)
+        R, t = transform(views.reshape(b * V, 6))
+        A, t = R.view(b, V, 3, 3), t.view(b, V, 3)
+        c = self._centroid.to(device=views.device, dtype=views.dtype).view(1, 1, 3)
+        if base_view is not None:
+            R0, t0 = transform(base_view.to(views.dtype))
+            t = t + t0.view(b, 1, 1, 3).matmul(A.transpose(3, 2)).squeeze(2)                  # R t0
+            A = A.matmul(R0.view(b, 1, 3, 3))
+        t = (c + t) - c.unsqueeze(0).matmul(A.transpose(3, 2)).squeeze(2)                     # - A c
+        return torch.cat([A.reshape(b, V, 9), t], 2).contiguous()
+
+    def render_pseudo_sweep(self, albedo, normal, depth, views, lights=None, mask=None, max_frames=None,
+                            base_view=None):
+        """The pseudo images of `sample_pseudo_imgs` for GIVEN views and lights, all frames in three launches per
+        chunk (g2s_sweep_verts, g2s_raster_depth_fwd, g2s_sweep_pseudo; csrc/sweep.hip) ->
+        (im (B,V,C,S,S), mask (B,V,1,S,S)).
+
+        Per frame this is relight + render_given_view(grid_sample=True): the canonical depth mesh posed by the view
+        and rasterised, the clamp of warp_canon_depth, the inverse warp, the bilinear read of the relit canonical
+        image clamped to [-1, 1] and the nearest read of the mask.  albedo (B,C,S,S); normal (B,S,S,3) canonical unit
+        normals; depth (B,S,S); views (V,6) or (B,V,6) in the units `set_transform_matrices` takes; lights (V,4) or
+        (B,V,4) raw (a, b, dx, dy) as the lighting net gives them (g2s_shading_fwd's convention), None = `albedo` is
+        sampled as given; mask (B,S,S) or (B,1,S,S), None = all ones.  base_view (B,6): every view is composed after
+        it (`pseudo_pose`).  Runs under no_grad, GPU only; frames go in chunks of at most `max_frames` (default: what
+        keeps the posed vertices of a chunk under 256 MiB) and the result does not depend on the chunking."""
+        from .. import lib as _lib
+        _lib.require_cuda(albedo, normal, depth, mask)
+        with torch.no_grad():
+            b, c, h, w = albedo.shape
+            dev = albedo.device
+            S = self.image_size
+            if (h, w) != (S, S) or tuple(depth.shape) != (b, S, S):
+                raise ValueError(f"albedo must be (B,C,{S},{S}) and depth (B,{S},{S}), got {tuple(albedo.shape)} and "
+                                 f"{tuple(depth.shape)}")
+            views = torch.as_tensor(views, dtype=torch.float32, device=dev)
+            if views.dim() not in (2, 3) or views.shape[-1] != 6 or (views.dim() == 3 and views.shape[0] != b):
+                raise ValueError(f"views must be (V, 6) or (B={b}, V, 6), got {tuple(views.shape)}")
+            V = views.shape[-2]
+            if lights is not None:
+                lights = torch.as_tensor(lights, dtype=torch.float32, device=dev)
+                lights = lights.expand(b, V, 4) if lights.dim() == 2 and lights.shape == (V, 4) else lights
+                if lights.shape != (b, V, 4):
+                    raise ValueError(f"lights must be (V, 4) or (B, V, 4) with V = {V}, got {tuple(lights.shape)}")
+                if normal is None:
+                    raise ValueError("relighting reads the canonical normals")
+            if mask is not None:
+                mask = mask.reshape(b, S, S) if mask.numel() == b * S * S else mask
+                if tuple(mask.shape) != (b, S, S):
+                    raise ValueError(f"mask must be (B,{S},{S}) or (B,1,{S},{S}), got {tuple(mask.shape)}")
+            bc, vc = sweep_chunks(b, V, max_frames, S * S * 12 + S * S * 4)
+            r = self.renderer
+            margin = (self.max_depth - self.min_depth) / 2
+            rays = self._pixel_rays(S, S, dev).reshape(-1, 3)
+            verts = (rays.unsqueeze(0) * depth.float().reshape(b, -1, 1)).contiguous()
+            pose = self.pseudo_pose(views, base_view, b)
+            K = self._K9
+            out = mout = None
+            for b0 in range(0, b, bc):
+                for v0 in range(0, V, vc):
+                    sb, sv = slice(b0, b0 + bc), slice(v0, v0 + vc)
+                    im_c, m_c = nr.pseudo_frames(
+                        verts[sb], pose[sb, sv], rays, K, albedo[sb], None if lights is None else normal[sb],
+                        None if lights is None else lights[sb, sv].reshape(-1, 4), None if mask is None else mask[sb],
+                        self.min_depth - margin, self.max_depth + margin, r.orig_size, S, r.anti_aliasing,
+                        r.fill_back)
+                    if bc >= b and vc >= V:
+                        out, mout = im_c, m_c
+                        break
+                    if out is None:
+                        out = torch.empty((b, V, c, S, S), dtype=torch.float32, device=dev)
+                        mout = torch.empty((b, V, S, S), dtype=torch.float32, device=dev)
+                    out[sb, sv] = im_c
+                    mout[sb, sv] = m_c
+        return out, mout.unsqueeze(2)
+
     def render_given_view(self, im, depth, view, mask=None, grid_sample=True):
         """renderer.py:252-277: warp `im` (and `mask`) to `view` — by inverse-warp sampling
         (grid_sample=True, the training path) or by rendering the textured mesh."""
@@ -373,6 +455,18 @@ class Renderer():
                                                     align_corners=True)
             return warped_images, warped_mask
         return warped_images
+
+
+def sweep_chunks(b, V, max_frames, bytes_per_frame, budget=256 << 20):
+    """(images, frames per image) of one chunk of a b x V sweep: at most `max_frames` frames (default: what keeps
+    `bytes_per_frame` x frames under `budget`), whole images first."""
+    if max_frames is None:
+        max_frames = max(1, budget // bytes_per_frame)
+    max_frames = int(max_frames)
+    if max_frames < 1:
+        raise ValueError("max_frames must be at least 1")
+    bc = min(b, max_frames)
+    return bc, min(V, max(1, max_frames // bc))
 
 
 def compose_sweep_pose(rotations, v_before, v_after, rot_center_depth, b=1):

@@ -255,6 +255,36 @@ int g2s_sweep_shade(const float *verts, const int32_t *faces, const int32_t *fac
                     int n_verts, int n_faces, int S, int ssaa, int C, int fill_back, int mode,
                     const float *background, float grey, float *rgb_out, float *alpha_out, g2s_stream_t stream);
 
+/* g2s_sweep_pseudo: the last launch of the pseudo-view path (Renderer.render_pseudo_sweep: g2s_sweep_verts,
+ * g2s_raster_depth_fwd, this).  It is the inverse-warp renderer of render_given_view(grid_sample=True) applied to the
+ * relit canonical image (GAN2Shape/model.py:291-328, renderer.py:252-264) for B*V frames in one pass, without forming
+ * the relit images, the sampling grid or a 3-channel mask.
+ * warped     [B*V, S, S] depth_out of g2s_raster_depth_fwd for the posed meshes, unclamped
+ * rays       [S*S, 3] K^-1 (u, v, 1)^T
+ * pose       [B, V, 12] the SAME affine map g2s_sweep_verts was given: row-major A, then t
+ * K          HOST pointer, 9 floats row-major (rows 0 and 1 are read)
+ * albedo     [B, C, S, S], C 1..4;  normal [B, S, S, 3] canonical unit normals, NULL iff light == NULL
+ * light      [B*V, 4] raw (a, b, dx, dy) as g2s_shading_fwd takes them, or NULL = no relighting
+ * mask       [B, S, S] canonical mask or NULL = all ones
+ * im_out     [B*V, C, S, S];  mask_out [B*V, S, S] or NULL
+ * Per output pixel p of frame f = b*V + v:
+ *     d = clamp(warped[f, p], depth_lo, depth_hi)                    (warp_canon_depth's clamp)
+ *     q = A^T (d ray_p - t)                                           (= R^T(d ray - t_view - c) + c of g2s_inv_warp_grid_fwd)
+ *     (gx, gy) = (K q / q.z)_xy * 2 / (S - 1) - 1                     (grid_3d_to_2d; q and K q / q.z are computed in double
+ *                                                                      and go to texel coordinates directly: the
+ *                                                                      normalisation cancels against grid_sample's)
+ *     im_out  = clamp(bilinear sample at (gx, gy), -1, 1), align_corners = True, zero padding, taps in the order
+ *               nw, ne, sw, se; a tap's value is (albedo / 2 + 0.5) * (a' + b' max(0, n . l)) * 2 - 1 with
+ *               a' = a / 2 + 0.5, b' = b / 2 + 0.5, l = (dx, dy, 1) / |(dx, dy, 1)| (g2s_shading_fwd's arithmetic),
+ *               or albedo as given when light == NULL
+ *     mask_out = nearest sample (round half to even, zero padding) of mask, or of an all-ones image
+ * One thread per output pixel; pose and light are wave-uniform loads; S need not be a multiple of anything.  No
+ * atomics: bit-identical from run to run and independent of how the caller chunks the frames.
+ * Every check precedes the launch: a rejected call leaves the outputs untouched. */
+int g2s_sweep_pseudo(const float *warped, const float *rays, const float *pose, const float *K, const float *albedo,
+                     const float *normal, const float *light, const float *mask, float depth_lo, float depth_hi,
+                     int B, int V, int S, int C, float *im_out, float *mask_out, g2s_stream_t stream);
+
 /* Sample generator (generate.py): the mapping network in one launch, the ordered mean, the image quantiser.
  * No backward.
  *
