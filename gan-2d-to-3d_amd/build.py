@@ -46,6 +46,7 @@ SOURCES = {
     "groupnorm.hip": [],
     "conv_wgrad.hip": [],
     "adam.hip": [],
+    "ada.hip": [],
     "probe.hip": [],
 }
 # The kernels take their descriptor struct by value.  Clang copies such a parameter into a private

@@ -944,6 +944,34 @@ int g2s_depth_metrics(const float *depth_pred, const float *depth_gt, const floa
                       const float *rays, int B, int H, int W, int erode, float *out, void *workspace,
                       size_t workspace_bytes, g2s_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------
+ * ADA augmentation (csrc/ada.hip): random_apply_affine and random_apply_color of stylegan2-pytorch/non_leaking.py
+ * with the SYM6 filter k (12 taps), f32, NCHW, two launches forward and two backward.
+ *
+ * g2s_ada_up2: x [B, C, H, W] -> x2 [B, C, 2 (H + py0 + py1), 2 (W + px0 + px1)].  Reflect padding by the four pads
+ *   (each 0 .. size - 1, as F.pad(mode='reflect') requires) and the separable 2x upsampling upfirdn(k, up 2,
+ *   pad (6, 5)) per axis, in one pass; no padded copy exists.
+ * g2s_ada_warp_down: x2 [B, C, H2, W2], Ginv [B, 2, 3], Cmat [B, 3, 4] or NULL -> y [B, C, H, W].
+ *   A = F.grid_sample(x2, F.affine_grid(Ginv, [B, C, 2 (H + 6), 2 (W + 6)], align_corners=False), 'bilinear',
+ *   'zeros', align_corners=False);  y = upfirdn(A, flipped k, down 2, pad (-1, -1)) on both axes;  with Cmat,
+ *   y[:, c] <- sum_c' Cmat[:, c, c'] y[:, c'] + Cmat[:, c, 3] (C must be 3).  A is never written to memory.
+ * g2s_ada_warp_down_bwd: gy [B, C, H, W] -> gx2 [B, C, H2, W2], the adjoint of the above in x2 (Cmat transposed).
+ *   Float atomics into gx2, which the call clears first unless acc_is_zero = 1 says it is zero already.  There is
+ *   no fixed-point variant: in deterministic mode (g2s_set_deterministic) the call returns G2S_ERR_INVALID.
+ * g2s_ada_up2_bwd: gx2 -> gx [B, C, H, W], the adjoint of g2s_ada_up2 (mirror images gathered, no atomics; every
+ *   element of gx is written).
+ * Ginv and Cmat get no gradient.  B * C <= 65535, H, W <= 16384.  Every check precedes the first launch; nothing
+ * allocates or synchronises.  All but g2s_ada_warp_down_bwd are bit-identical from run to run.
+ * ---------------------------------------------------------------------------------------- */
+int g2s_ada_up2(const float *x, float *x2, int B, int C, int H, int W, int px0, int px1, int py0, int py1,
+                g2s_stream_t stream);
+int g2s_ada_up2_bwd(const float *gx2, float *gx, int B, int C, int H, int W, int px0, int px1, int py0, int py1,
+                    g2s_stream_t stream);
+int g2s_ada_warp_down(const float *x2, const float *Ginv, const float *Cmat, float *y, int B, int C, int H, int W,
+                      int H2, int W2, g2s_stream_t stream);
+int g2s_ada_warp_down_bwd(const float *gy, const float *Ginv, const float *Cmat, float *gx2, int B, int C, int H,
+                          int W, int H2, int W2, int acc_is_zero, g2s_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
