@@ -34,13 +34,8 @@ struct LightParams {
 // Vertex ids and the un-normalised normal of face g of image b; false when an id is out of range.
 __device__ __forceinline__ bool face_cross(const LightParams &p, int b, int g, int v[3], float a[3], float e[3],
                                            float c[3]) {
-    if (p.faces) {
-        v[0] = p.faces[3 * g];
-        v[1] = p.faces[3 * g + 1];
-        v[2] = p.faces[3 * g + 2];
-    } else {
-        implicit_face(g, p.S, v);
-    }
+    bool rev;
+    winner_verts(g, p.F, p.S, p.faces, false, g, rev, v);   // g < F: the face itself, never its reversed copy
     for (int k = 0; k < 3; k++)
         if ((unsigned)v[k] >= (unsigned)p.N) return false;
     const float *q0 = p.verts + ((size_t)b * p.N + v[0]) * 3;
@@ -116,14 +111,6 @@ __global__ __launch_bounds__(256) void face_light_bwd_kernel(LightParams p) {
     }
 }
 
-template <bool ADD>
-__global__ __launch_bounds__(256) void face_light_bwd_unfix(const long long *fix, float *out, long n) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float s = from_fix(fix[i]);
-    out[i] = ADD ? out[i] + s : s;
-}
-
 static int light_args(LightParams &p, const float *verts, const int32_t *faces, int B, int n_verts, int n_faces, int S,
                       int fill_back, const float *directional, const float *direction) {
     G2S_REQUIRE(verts && directional && direction, "NULL pointer argument");
@@ -168,29 +155,25 @@ extern "C" int g2s_face_light_bwd(const float *verts, const int32_t *faces, cons
                                   size_t workspace_bytes, int acc_is_zero, g2s_stream_t stream) {
     G2S_REQUIRE(grad_light && grad_verts, "NULL pointer argument");
     LightParams p{};
-    const int rc = light_args(p, verts, faces, B, n_verts, n_faces, S, fill_back, directional, direction);
+    int rc = light_args(p, verts, faces, B, n_verts, n_faces, S, fill_back, directional, direction);
     if (rc) return rc;
     p.grad_light = grad_light;
     hipStream_t st = as_stream(stream);
     const size_t nv = (size_t)B * n_verts * 3;
     const int blocks = cdiv((long)B * n_faces, 256);
-    if (deterministic()) {
-        const size_t need = g2s_raster_bwd_workspace_bytes(B, n_verts);
-        if (!workspace || workspace_bytes < need)
-            return fail(G2S_ERR_WORKSPACE, "deterministic mode: the backward needs its fixed-point workspace "
-                        "(g2s_raster_bwd_workspace_bytes = %zu bytes, got %zu)", need,
-                        workspace ? workspace_bytes : (size_t)0);
-        long long *fix = reinterpret_cast<long long *>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    const ScatterTarget target{grad_verts, nv, "grad_verts"};
+    long long *fix;
+    rc = scatter_begin("g2s_raster_bwd", g2s_raster_bwd_workspace_bytes(B, n_verts), workspace, workspace_bytes,
+                       acc_is_zero, st, &target, 1, fix);
+    if (rc) return rc;
+    if (fix) {
         p.gver = fix;
-        if (!acc_is_zero && hipMemsetAsync(fix, 0, nv * sizeof(long long), st) != hipSuccess)
-            return fail(G2S_ERR_LAUNCH, "hipMemsetAsync(workspace) failed");
         face_light_bwd_kernel<long long><<<blocks, 256, 0, st>>>(p);
-        if (acc_is_zero) face_light_bwd_unfix<true><<<cdiv((long)nv, 256), 256, 0, st>>>(fix, grad_verts, (long)nv);
-        else face_light_bwd_unfix<false><<<cdiv((long)nv, 256), 256, 0, st>>>(fix, grad_verts, (long)nv);
+        // as in default mode, where the atomics add onto whatever an uncleared grad_verts holds
+        if (acc_is_zero) scatter_unfix<true><<<cdiv((long)nv, 256), 256, 0, st>>>(fix, grad_verts, (long)nv);
+        else scatter_unfix<false><<<cdiv((long)nv, 256), 256, 0, st>>>(fix, grad_verts, (long)nv);
     } else {
         p.gver = grad_verts;
-        if (!acc_is_zero && hipMemsetAsync(grad_verts, 0, nv * sizeof(float), st) != hipSuccess)
-            return fail(G2S_ERR_LAUNCH, "hipMemsetAsync(grad_verts) failed");
         face_light_bwd_kernel<float><<<blocks, 256, 0, st>>>(p);
     }
     return check_launch("g2s_face_light_bwd");

@@ -25,7 +25,9 @@
 //           ~70 candidate faces per tile instead of 64 516.
 //   bwd     lane = raster sample of an 8x8 tile: analytic gradient to the three projected vertices,
 //           neighbouring samples of the same face merged by shuffles, then float atomics; one
-//           thread per vertex for the projection backward.
+//           thread per vertex for the projection backward.  The winner decode is raster_core.h's
+//           winner_verts; accumulator prologue, merge, vertex table and projection kernel are
+//           raster_scatter.h's, shared with raster_rgb.hip.
 //
 // Compiled with -ffp-contract=off: results equal oracle/raster_body.inc bit for bit up to the
 // association order of the 2x2 average.
@@ -412,20 +414,9 @@ __global__ __launch_bounds__(64 * WAVES) void raster_tiles(RasterParams p) {
         // weights of the winning fragment: same arithmetic on the same inputs as when it was queued
         float w[3] = {0.0f, 0.0f, 0.0f};
         if (!bg) {
-            int v[3];
-            const int g = best_fn % p.F;
-            if (IMPLICIT) {
-                implicit_face(g, p.S, v);
-            } else {
-                v[0] = p.faces[3 * g];
-                v[1] = p.faces[3 * g + 1];
-                v[2] = p.faces[3 * g + 2];
-            }
-            if (best_fn >= p.F) {
-                const int tmp = v[0];
-                v[0] = v[2];
-                v[2] = tmp;
-            }
+            int v[3], g;
+            bool rev;
+            winner_verts(best_fn, p.F, p.S, IMPLICIT ? nullptr : p.faces, true, g, rev, v);
             const float4 q0 = proj[v[0]], q1 = proj[v[1]], q2 = proj[v[2]];
             float fi[9], zp;
             face_inverse(q0.x, q0.y, q1.x, q1.y, q2.x, q2.y, p.is, fi);
@@ -486,19 +477,9 @@ __global__ __launch_bounds__(256) void raster_bwd_samples(BwdParams p) {
     int v[3] = {0, 0, 0};
     float acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (fn >= 0) {
-        const int gidx = fn % p.F;
-        if (p.faces) {
-            v[0] = p.faces[3 * gidx];
-            v[1] = p.faces[3 * gidx + 1];
-            v[2] = p.faces[3 * gidx + 2];
-        } else {
-            implicit_face(gidx, p.S, v);
-        }
-        if (fn >= p.F) {
-            const int t = v[0];
-            v[0] = v[2];
-            v[2] = t;
-        }
+        int gidx;
+        bool rev;
+        winner_verts(fn, p.F, p.S, p.faces, true, gidx, rev, v);
         float px[3], py[3], pz[3];
         for (int k = 0; k < 3; k++) {
             const float *q = p.verts + ((size_t)b * p.N + v[k]) * 3;
@@ -522,12 +503,6 @@ __global__ __launch_bounds__(256) void raster_bwd_samples(BwdParams p) {
     if (fn >= 0)
         for (int k = 0; k < 3; k++) vt_add(table[wave], v[k], acc[3 * k], acc[3 * k + 1], acc[3 * k + 2], gout_b);
     vt_flush(table[wave], lane, gout_b);
-}
-
-__global__ __launch_bounds__(256) void raster_bwd_project(BwdParams p) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)p.B * p.N) return;
-    project_backward_vertex(p.verts, p.gacc, p.gfix, p.cam, i);
 }
 
 static int implicit_blocks(int S) { return (S - 1 + 7) / 8; }
@@ -654,23 +629,14 @@ extern "C" int g2s_raster_depth_bwd_ex(const float *verts, const int32_t *faces,
     p.is = S * ssaa;
     p.gacc = grad_verts;
     hipStream_t st = as_stream(stream);
-    const int bw_tiles = cdiv(p.is, TILE) * cdiv(p.is, TILE);
-    if (deterministic()) {
-        // float atomics would make the vertex sums depend on the order the tiles finish in
-        if (!workspace || workspace_bytes < g2s_raster_bwd_workspace_bytes(B, n_verts))
-            return fail(G2S_ERR_WORKSPACE, "deterministic mode: the backward needs its fixed-point workspace "
-                        "(g2s_raster_bwd_workspace_bytes = %zu bytes, got %zu)",
-                        g2s_raster_bwd_workspace_bytes(B, n_verts), workspace ? workspace_bytes : (size_t)0);
-        p.gfix = reinterpret_cast<long long *>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-        if (!acc_is_zero && hipMemsetAsync(p.gfix, 0, (size_t)B * n_verts * 3 * sizeof(long long), st) != hipSuccess)
-            return fail(G2S_ERR_LAUNCH, "hipMemsetAsync(workspace) failed");
-        raster_bwd_samples<long long><<<dim3(cdiv(bw_tiles, 4), B), 256, 0, st>>>(p);
-    } else {
-        if (!acc_is_zero && hipMemsetAsync(grad_verts, 0, (size_t)B * n_verts * 3 * sizeof(float), st) != hipSuccess)
-            return fail(G2S_ERR_LAUNCH, "hipMemsetAsync(grad_verts) failed");
-        raster_bwd_samples<float><<<dim3(cdiv(bw_tiles, 4), B), 256, 0, st>>>(p);
-    }
-    raster_bwd_project<<<cdiv((long)B * n_verts, 256), 256, 0, st>>>(p);
+    const dim3 grid(cdiv(cdiv(p.is, TILE) * cdiv(p.is, TILE), 4), B);
+    const ScatterTarget target{grad_verts, (size_t)B * n_verts * 3, "grad_verts"};
+    rc = scatter_begin("g2s_raster_bwd", g2s_raster_bwd_workspace_bytes(B, n_verts), workspace, workspace_bytes,
+                       acc_is_zero, st, &target, 1, p.gfix);
+    if (rc) return rc;
+    if (p.gfix) raster_bwd_samples<long long><<<grid, 256, 0, st>>>(p);
+    else raster_bwd_samples<float><<<grid, 256, 0, st>>>(p);
+    scatter_project<<<cdiv((long)B * n_verts, 256), 256, 0, st>>>(verts, grad_verts, p.gfix, p.cam, (long)B * n_verts);
     return check_launch("g2s_raster_depth_bwd");
 }
 

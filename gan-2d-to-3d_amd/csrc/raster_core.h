@@ -172,6 +172,28 @@ G2S_HD void implicit_face(int g, int S, int v[3]) {
     }
 }
 
+// Winner id of one raster sample (what the depth pass stores in face_idx) -> the geometric face g = fn % F,
+// whether it is the reversed fill_back copy (ids >= F, when the caller's ids carry one: `reversible`), and the
+// vertex triple in the order the face was drawn: from the face list, or from the implicit grid when `faces` is
+// NULL, with v0 and v2 swapped for the reversed copy.  The one statement of that rule: every pass that reads the
+// maps decodes a winner here, and face_light.hip takes its un-reversed triples from it too.
+G2S_HD void winner_verts(int fn, int F, int S, const int32_t *faces, bool reversible, int &g, bool &rev, int v[3]) {
+    g = fn % F;
+    rev = reversible && fn >= F;
+    if (faces) {
+        v[0] = faces[3 * g];
+        v[1] = faces[3 * g + 1];
+        v[2] = faces[3 * g + 2];
+    } else {
+        implicit_face(g, S, v);
+    }
+    if (rev) {
+        const int t = v[0];
+        v[0] = v[2];
+        v[2] = t;
+    }
+}
+
 // backward_depth_map [recalled] for one raster sample + projection backward.
 // Inputs: projected face (x,y,z per vertex), saved weights, incoming gradient g (already divided
 // by the pooling factor).  Outputs gradient w.r.t. the projected vertices (gx, gy, gz per vertex).

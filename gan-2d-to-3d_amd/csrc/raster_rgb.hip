@@ -18,9 +18,15 @@
 // (face_light.hip, indexed by the winner id) multiplies the sample's colour before background selection, and
 // alpha is the share of a pixel's samples that have a winner.  The unlit entry points call the same launchers
 // with light = alpha_out = grad_light = NULL and run the same template instances as before.
+//
+// What this file shares is stated elsewhere, once: the winner decode in raster_core.h (winner_verts); the
+// perspective weights, the cube coordinates with their clamp state (CubeCoord: forward and the three gradient
+// sections read the same cells with the same weights) and the pixel resolve in shade_core.h; the accumulator
+// prologue, the merge, the vertex table and the unfix / projection kernels in raster_scatter.h.
 #include "g2s_common.h"
 #include "raster_core.h"
 #include "raster_scatter.h"
+#include "shade_core.h"
 
 namespace g2s {
 
@@ -48,55 +54,17 @@ __device__ __forceinline__ bool sample_colour(const RgbParams &p, int b, int yi,
         for (int c = 0; c < p.C; c++) col[c] = p.bg[c];
         return false;
     }
-    const int g = fn % p.F;
-    const bool rev = fn >= p.F;
-    int v[3];
-    if (IMPLICIT) {
-        implicit_face(g, p.S, v);
-    } else {
-        v[0] = p.faces[3 * g];
-        v[1] = p.faces[3 * g + 1];
-        v[2] = p.faces[3 * g + 2];
-    }
-    if (rev) {
-        const int t = v[0];
-        v[0] = v[2];
-        v[2] = t;
-    }
-    float w[3], z[3];
+    int g, v[3];
+    bool rev;
+    winner_verts(fn, p.F, p.S, IMPLICIT ? nullptr : p.faces, true, g, rev, v);
+    float w[3], z[3], a[3];
     for (int k = 0; k < 3; k++) {
         w[k] = p.bary[3 * si + k];
         z[k] = p.verts[((size_t)b * p.N + v[k]) * 3 + 2];
     }
-    const float depth = 1.0f / (w[0] / z[0] + w[1] / z[1] + w[2] / z[2]);
+    const float depth = persp_weights(w, z, a);
     const int ts = p.ts;
-    float tf[3];
-    int ti[3];
-    for (int k = 0; k < 3; k++) {
-        float t = w[k] * (float)(ts - 1) * (depth / z[k]);
-        t = fmaxf(t, 0.0f);
-        t = fminf(t, (float)(ts - 1) - p.eps);
-        ti[k] = (int)t;
-        tf[k] = t - (float)ti[k];
-    }
-    const float *tex = p.tex + ((size_t)b * p.F + g) * ts * ts * ts * p.C;
-    for (int c = 0; c < p.C; c++) col[c] = 0.0f;
-    for (int pn = 0; pn < 8; pn++) {
-        float wt = 1.0f;
-        int idx[3];
-        for (int k = 0; k < 3; k++) {
-            if (((pn >> k) & 1) == 0) {
-                wt *= 1.0f - tf[k];
-                idx[k] = ti[k];
-            } else {
-                wt *= tf[k];
-                idx[k] = min(ti[k] + 1, ts - 1);   // weight 0 there when ts == 1
-            }
-        }
-        // the reversed copy's cube is textures.permute(0, 1, 4, 3, 2, 5): axes 0 and 2 swapped
-        const int isc = rev ? (idx[2] * ts + idx[1]) * ts + idx[0] : (idx[0] * ts + idx[1]) * ts + idx[2];
-        for (int c = 0; c < p.C; c++) col[c] += wt * tex[(size_t)isc * p.C + c];
-    }
+    cube_coord(w, z, depth, ts, p.eps).read(p.tex + ((size_t)b * p.F + g) * ts * ts * ts * p.C, rev, ts, p.C, col);
     if (EXTRA && p.light) {
         const float *l = p.light + ((size_t)b * p.Ftot + min(fn, p.Ftot - 1)) * 3;
         for (int c = 0; c < 3; c++) col[c] *= l[c];
@@ -108,33 +76,18 @@ template <bool IMPLICIT, bool EXTRA>
 __global__ void raster_rgb_kernel(RgbParams p) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)p.B * p.S * p.S) return;
-    const int b = (int)(i / ((long)p.S * p.S));
-    const int r = (int)((i / p.S) % p.S), c0 = (int)(i % p.S);
-    float sum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    int covered = 0;
-    for (int dy = 0; dy < p.ssaa; dy++)
-        for (int dx = 0; dx < p.ssaa; dx++) {
-            const int yi = p.is - 1 - (r * p.ssaa + dy);   // row of the (unflipped) raster
-            float col[4];
-            if (sample_colour<IMPLICIT, EXTRA>(p, b, yi, c0 * p.ssaa + dx, col)) covered++;
-            for (int c = 0; c < p.C; c++) sum[c] += col[c];
-        }
-    const float inv = 1.0f / (float)(p.ssaa * p.ssaa);
-    for (int c = 0; c < p.C; c++) p.out[(((size_t)b * p.C + c) * p.S + r) * p.S + c0] = sum[c] * inv;
-    if (EXTRA && p.alpha) p.alpha[((size_t)b * p.S + r) * p.S + c0] = (float)covered * inv;
+    resolve_pixel(i, p.S, p.ssaa, p.C, p.out, EXTRA ? p.alpha : nullptr, [&](int b, int yi, int xi, float col[4]) {
+        return sample_colour<IMPLICIT, EXTRA>(p, b, yi, xi, col);
+    });
 }
 
-// Alpha alone (nr.Renderer.render_silhouettes): no texture is read.
+// Alpha alone (nr.Renderer.render_silhouettes): the resolve with no colour channels, no texture is read.
 __global__ void raster_alpha_kernel(const int32_t *face_idx, float *alpha, int B, int S, int ssaa) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)B * S * S) return;
-    const int b = (int)(i / ((long)S * S));
-    const int r = (int)((i / S) % S), c0 = (int)(i % S), is = S * ssaa;
-    int covered = 0;
-    for (int dy = 0; dy < ssaa; dy++)
-        for (int dx = 0; dx < ssaa; dx++)
-            if (face_idx[((size_t)b * is + (is - 1 - (r * ssaa + dy))) * is + c0 * ssaa + dx] >= 0) covered++;
-    alpha[i] = (float)covered * (1.0f / (float)(ssaa * ssaa));
+    const int is = S * ssaa;
+    resolve_pixel(i, S, ssaa, 0, nullptr, alpha,
+                  [&](int b, int yi, int xi, float *) { return face_idx[((size_t)b * is + yi) * is + xi] >= 0; });
 }
 
 // ---------------------------------------------------------------------------------- backward
@@ -195,61 +148,27 @@ __global__ __launch_bounds__(256) void raster_rgb_bwd_samples(RgbBwdParams p) {
         if (!any) fn = -1;  // masked pixels contribute exact zeros
     }
     int v[3] = {0, 0, 0};
-    int ti[3] = {0, 0, 0};
-    float w[3] = {0, 0, 0}, z[3] = {1, 1, 1}, tf[3] = {0, 0, 0}, a[3] = {0, 0, 0};
+    float w[3] = {0, 0, 0}, z[3] = {1, 1, 1}, a[3] = {0, 0, 0};
     float depth = 0.0f;
-    bool live[3] = {false, false, false};  // t_k strictly between its clamps
+    CubeCoord cc{};   // the forward's lookup position, from the same saved weights: same cell, same clamp state
     bool rev = false;
     int gidx = 0;
     if (fn >= 0) {
-        gidx = fn % p.F;
-        rev = fn >= p.F;
-        if (p.faces) {
-            v[0] = p.faces[3 * gidx];
-            v[1] = p.faces[3 * gidx + 1];
-            v[2] = p.faces[3 * gidx + 2];
-        } else {
-            implicit_face(gidx, p.S, v);
-        }
-        if (rev) {
-            const int t = v[0];
-            v[0] = v[2];
-            v[2] = t;
-        }
+        winner_verts(fn, p.F, p.S, p.faces, true, gidx, rev, v);
         for (int k = 0; k < 3; k++) {
             w[k] = p.bary[3 * si + k];
             z[k] = p.verts[((size_t)b * p.N + v[k]) * 3 + 2];
-            a[k] = w[k] / z[k];
         }
-        depth = 1.0f / (a[0] + a[1] + a[2]);
-        const float hi = (float)(ts - 1) - p.eps;
-        for (int k = 0; k < 3; k++) {
-            const float tu = w[k] * (float)(ts - 1) * (depth / z[k]);
-            live[k] = tu > 0.0f && tu < hi;
-            float t = fmaxf(tu, 0.0f);
-            t = fminf(t, hi);
-            ti[k] = (int)t;
-            tf[k] = t - (float)ti[k];
-        }
+        depth = persp_weights(w, z, a);
+        cc = cube_coord(w, z, depth, ts, p.eps);
     }
-    // cell of corner pn in the geometric face's cube (the reversed copy reads it with axes 0 and 2 swapped)
-    auto cell = [&](int pn) {
-        int idx[3];
-        for (int k = 0; k < 3; k++) idx[k] = ((pn >> k) & 1) ? min(ti[k] + 1, ts - 1) : ti[k];
-        return rev ? (idx[2] * ts + idx[1]) * ts + idx[0] : (idx[0] * ts + idx[1]) * ts + idx[2];
-    };
     const size_t cube = ((size_t)b * p.F + gidx) * ts * ts * ts * p.C;
 
     if (LIT) {
         float lp[3] = {0.0f, 0.0f, 0.0f};
         if (fn >= 0) {
             if (p.glight) {  // grad_colour * unlit colour: the forward's trilinear read again
-                for (int pn = 0; pn < 8; pn++) {
-                    float wt = 1.0f;
-                    for (int k = 0; k < 3; k++) wt *= ((pn >> k) & 1) ? tf[k] : 1.0f - tf[k];
-                    const float *tx = p.tex + cube + (size_t)cell(pn) * 3;
-                    for (int c = 0; c < 3; c++) lp[c] += wt * tx[c];
-                }
+                cc.read(p.tex + cube, rev, ts, 3, lp);
                 for (int c = 0; c < 3; c++) lp[c] *= g[c];
             }
             const float *l = p.light + ((size_t)b * p.Ftot + min(fn, p.Ftot - 1)) * 3;
@@ -271,9 +190,7 @@ __global__ __launch_bounds__(256) void raster_rgb_bwd_samples(RgbBwdParams p) {
             float part[32];
 #pragma unroll
             for (int pn = 0; pn < 8; pn++) {
-                float wt = 1.0f;
-#pragma unroll
-                for (int k = 0; k < 3; k++) wt *= ((pn >> k) & 1) ? tf[k] : 1.0f - tf[k];
+                const float wt = cc.weight(pn);
 #pragma unroll
                 for (int c = 0; c < 4; c++) part[4 * pn + c] = fn >= 0 ? wt * g[c] : 0.0f;
             }
@@ -282,7 +199,7 @@ __global__ __launch_bounds__(256) void raster_rgb_bwd_samples(RgbBwdParams p) {
             if (ft >= 0) {
 #pragma unroll
                 for (int pn = 0; pn < 8; pn++) {
-                    ACC *dst = gt + cube + (size_t)cell(pn) * p.C;
+                    ACC *dst = gt + cube + (size_t)cc.cell(pn, rev, ts) * p.C;
 #pragma unroll
                     for (int c = 0; c < 4; c++)
                         if (c < p.C) acc_add(dst + c, part[4 * pn + c]);
@@ -290,10 +207,9 @@ __global__ __launch_bounds__(256) void raster_rgb_bwd_samples(RgbBwdParams p) {
             }
         } else if (fn >= 0) {
             for (int pn = 0; pn < 8; pn++) {
-                float wt = 1.0f;
-                for (int k = 0; k < 3; k++) wt *= ((pn >> k) & 1) ? tf[k] : 1.0f - tf[k];
+                const float wt = cc.weight(pn);
                 if (wt == 0.0f) continue;
-                ACC *dst = gt + cube + (size_t)cell(pn) * p.C;
+                ACC *dst = gt + cube + (size_t)cc.cell(pn, rev, ts) * p.C;
 #pragma unroll
                 for (int c = 0; c < 4; c++)
                     if (c < p.C) acc_add(dst + c, wt * g[c]);
@@ -305,24 +221,23 @@ __global__ __launch_bounds__(256) void raster_rgb_bwd_samples(RgbBwdParams p) {
         ACC *const gout_b = reinterpret_cast<ACC *>(p.gver) + (size_t)b * p.N * 3;
         int fv = fn;
         float acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        if (fv >= 0 && !(live[0] || live[1] || live[2])) fv = -1;  // constant under every clamp: exact zeros
+        if (fv >= 0 && !(cc.live[0] || cc.live[1] || cc.live[2])) fv = -1;  // constant under every clamp: exact zeros
         if (fv >= 0) {
             // d colour . g / d t_k: the corner sums with the k-th factor replaced by its derivative (-1, +1)
             float gtk[3] = {0.0f, 0.0f, 0.0f};
             for (int pn = 0; pn < 8; pn++) {
-                const float *tx = p.tex + cube + (size_t)cell(pn) * p.C;
+                const float *tx = p.tex + cube + (size_t)cc.cell(pn, rev, ts) * p.C;
                 float s = 0.0f;
 #pragma unroll
                 for (int c = 0; c < 4; c++)
                     if (c < p.C) s += g[c] * tx[c];
-                float f[3];
-                for (int k = 0; k < 3; k++) f[k] = ((pn >> k) & 1) ? tf[k] : 1.0f - tf[k];
+                const float f[3] = {cc.factor(pn, 0), cc.factor(pn, 1), cc.factor(pn, 2)};
                 gtk[0] += (((pn >> 0) & 1) ? s : -s) * (f[1] * f[2]);
                 gtk[1] += (((pn >> 1) & 1) ? s : -s) * (f[0] * f[2]);
                 gtk[2] += (((pn >> 2) & 1) ? s : -s) * (f[0] * f[1]);
             }
             for (int k = 0; k < 3; k++)
-                if (!live[k]) gtk[k] = 0.0f;
+                if (!cc.live[k]) gtk[k] = 0.0f;
             // t_k = (ts - 1) a_k D, D = 1 / sum_j a_j:  g_a[j] = (ts - 1) D (g_t[j] - D sum_k g_t[k] a_k)
             const float dot = (gtk[0] * a[0] + gtk[1] * a[1] + gtk[2] * a[2]) * depth;
             float gw[3], gz[3];
@@ -352,17 +267,6 @@ __global__ __launch_bounds__(256) void raster_rgb_bwd_samples(RgbBwdParams p) {
             for (int k = 0; k < 3; k++) vt_add(table[wave], v[k], acc[3 * k], acc[3 * k + 1], acc[3 * k + 2], gout_b);
         vt_flush(table[wave], lane, gout_b);
     }
-}
-
-__global__ __launch_bounds__(256) void raster_rgb_bwd_project(const float *verts, float *gacc, const long long *gfix,
-                                                              Cam cam, long n) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) project_backward_vertex(verts, gacc, gfix, cam, i);
-}
-
-__global__ __launch_bounds__(256) void raster_rgb_bwd_unfix(const long long *fix, float *out, long n) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = from_fix(fix[i]);
 }
 
 template <typename ACC, bool MERGE, bool LIT>
@@ -477,7 +381,7 @@ static int rgb_bwd(const char *who, const float *verts, const int32_t *faces, co
     G2S_REQUIRE(faces || (n_verts == S * S && n_faces == 2 * (S - 1) * (S - 1)),
                 "implicit topology needs S*S vertices and 2(S-1)^2 faces");
     RgbBwdParams p{};
-    const int rc = make_cam(K, orig_size, p.cam);
+    int rc = make_cam(K, orig_size, p.cam);
     if (rc) return rc;
     p.verts = verts;
     p.faces = faces;
@@ -500,44 +404,31 @@ static int rgb_bwd(const char *who, const float *verts, const int32_t *faces, co
     const size_t nt = rgb_bwd_tex_elems(B, n_faces, ts, C), nv = (size_t)B * n_verts * 3;
     const size_t nl = grad_light ? (size_t)B * p.Ftot * 3 : 0;
     const bool want_t = grad_textures != nullptr, want_v = grad_verts != nullptr;
-    if (deterministic()) {
-        // float atomics would make the sums depend on the order the tiles finish in
-        const size_t need = g2s_raster_rgb_bwd_workspace_bytes(B, n_verts, n_faces, ts, C) + nl * sizeof(long long);
-        if (!workspace || workspace_bytes < need)
-            return fail(G2S_ERR_WORKSPACE, "deterministic mode: the backward needs its fixed-point workspace "
-                        "(%s_workspace_bytes = %zu bytes, got %zu)", who, need,
-                        workspace ? workspace_bytes : (size_t)0);
-        long long *fix = reinterpret_cast<long long *>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    // in the fixed-point workspace: textures, then vertices, then light
+    const ScatterTarget targets[3] = {{grad_light, nl, "grad_light"}, {grad_textures, nt, "grad_textures"},
+                                      {grad_verts, nv, "grad_verts"}};
+    const size_t need = g2s_raster_rgb_bwd_workspace_bytes(B, n_verts, n_faces, ts, C) + nl * sizeof(long long);
+    long long *fix;
+    rc = scatter_begin(who, need, workspace, workspace_bytes, acc_is_zero, st, targets, 3, fix);
+    if (rc) return rc;
+    if (fix) {
         p.gtex = fix;
         p.gver = fix + nt;
         p.glight = grad_light ? fix + nt + nv : nullptr;
-        if (!acc_is_zero && hipMemsetAsync(fix, 0, (nt + nv + nl) * sizeof(long long), st) != hipSuccess)
-            return fail(G2S_ERR_LAUNCH, "hipMemsetAsync(workspace) failed");
         if (ts == 2) launch_rgb_bwd<long long, true>(p, want_t, want_v, st);
         else launch_rgb_bwd<long long, false>(p, want_t, want_v, st);
-        if (want_t) raster_rgb_bwd_unfix<<<cdiv((long)nt, 256), 256, 0, st>>>(fix, grad_textures, (long)nt);
-        if (grad_light) raster_rgb_bwd_unfix<<<cdiv((long)nl, 256), 256, 0, st>>>(fix + nt + nv, grad_light, (long)nl);
-        if (want_v)
-            raster_rgb_bwd_project<<<cdiv((long)B * n_verts, 256), 256, 0, st>>>(verts, grad_verts, fix + nt, p.cam,
-                                                                                  (long)B * n_verts);
+        if (want_t) scatter_unfix<false><<<cdiv((long)nt, 256), 256, 0, st>>>(fix, grad_textures, (long)nt);
+        if (grad_light) scatter_unfix<false><<<cdiv((long)nl, 256), 256, 0, st>>>(fix + nt + nv, grad_light, (long)nl);
     } else {
         p.gtex = grad_textures;
         p.gver = grad_verts;
         p.glight = grad_light;
-        if (!acc_is_zero) {
-            if (grad_light && hipMemsetAsync(grad_light, 0, nl * sizeof(float), st) != hipSuccess)
-                return fail(G2S_ERR_LAUNCH, "hipMemsetAsync(grad_light) failed");
-            if (want_t && hipMemsetAsync(grad_textures, 0, nt * sizeof(float), st) != hipSuccess)
-                return fail(G2S_ERR_LAUNCH, "hipMemsetAsync(grad_textures) failed");
-            if (want_v && hipMemsetAsync(grad_verts, 0, nv * sizeof(float), st) != hipSuccess)
-                return fail(G2S_ERR_LAUNCH, "hipMemsetAsync(grad_verts) failed");
-        }
         if (ts == 2) launch_rgb_bwd<float, true>(p, want_t, want_v, st);
         else launch_rgb_bwd<float, false>(p, want_t, want_v, st);
-        if (want_v)
-            raster_rgb_bwd_project<<<cdiv((long)B * n_verts, 256), 256, 0, st>>>(verts, grad_verts, nullptr, p.cam,
-                                                                                  (long)B * n_verts);
     }
+    if (want_v)
+        scatter_project<<<cdiv((long)B * n_verts, 256), 256, 0, st>>>(verts, grad_verts, fix ? fix + nt : nullptr, p.cam,
+                                                                      (long)B * n_verts);
     return check_launch(who);
 }
 

@@ -1,9 +1,11 @@
-// raster_scatter.h — gradient scatter shared by the rasterizer's two backward passes (raster.hip:
-// depth, raster_rgb.hip: texture lookup).  Both run one wave per 8x8-sample tile, lane = raster
-// sample, and end the same way: neighbouring samples of one face merge their partial sums through
-// shuffles, the per-vertex partials of a tile meet in a per-wave LDS table keyed by vertex id, each
-// distinct vertex reaches memory once, and one thread per vertex maps (g_u, g_v, g_z) of the
-// projected vertex back to camera xyz.  Device code only (HIP).
+// raster_scatter.h — gradient scatter shared by the rasterizer's backward passes (raster.hip: depth,
+// raster_rgb.hip: texture lookup, face_light.hip: per-face light).  The first two run one wave per
+// 8x8-sample tile, lane = raster sample, and end the same way: neighbouring samples of one face merge
+// their partial sums through shuffles, the per-vertex partials of a tile meet in a per-wave LDS table
+// keyed by vertex id, each distinct vertex reaches memory once, and one thread per vertex maps
+// (g_u, g_v, g_z) of the projected vertex back to camera xyz (scatter_project).  All three start with
+// the same host prologue (scatter_begin: float accumulators, or 2^-40 fixed point in deterministic
+// mode, cleared unless the caller did) and turn fixed-point sums back with scatter_unfix.  HIP only.
 #pragma once
 #include "g2s_common.h"
 #include "raster_core.h"
@@ -103,10 +105,12 @@ __device__ __forceinline__ void vt_flush(VertexTable<ACC> &t, int lane, ACC *gou
     }
 }
 
-// Vertex i of [B * N]: (g_u, g_v, g_z) of the projected vertex, summed in gacc (or as fixed point in
-// gfix when that is given), becomes the gradient w.r.t. camera xyz, in place in gacc.
-__device__ __forceinline__ void project_backward_vertex(const float *verts, float *gacc, const long long *gfix,
-                                                        const Cam &cam, long i) {
+// One thread per vertex i of [B * N]: (g_u, g_v, g_z) of the projected vertex, summed in gacc (or as fixed
+// point in gfix when that is given), becomes the gradient w.r.t. camera xyz, in place in gacc.
+static __global__ __launch_bounds__(256) void scatter_project(const float *verts, float *gacc, const long long *gfix,
+                                                              Cam cam, long n) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
     const float *q = verts + i * 3;
     float *g = gacc + i * 3;
     float gx, gy, gz;
@@ -121,10 +125,54 @@ __device__ __forceinline__ void project_backward_vertex(const float *verts, floa
     g[2] = gz;
 }
 
+// Fixed-point sums back to float: out = fix, or out += fix for a target that already holds a gradient (ADD).
+template <bool ADD>
+__global__ __launch_bounds__(256) void scatter_unfix(const long long *fix, float *out, long n) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float s = from_fix(fix[i]);
+    out[i] = ADD ? out[i] + s : s;
+}
+
 static int make_cam(const float *K, float orig_size, Cam &c) {
     G2S_REQUIRE(K != nullptr, "K must be a host pointer to 9 floats");
     G2S_REQUIRE(K[6] == 0.0f && K[7] == 0.0f && K[8] == 1.0f, "K third row must be 0 0 1");
     c = Cam{K[0], K[1], K[2], K[3], K[4], K[5], orig_size};
+    return G2S_OK;
+}
+
+// One float gradient a backward scatters into: n elements at ptr (ptr may be NULL: not wanted in default mode;
+// its n still counts in the fixed-point layout), `name` as the messages call it.
+struct ScatterTarget {
+    float *ptr;
+    size_t n;
+    const char *name;
+};
+
+// Host prologue of a scattering backward: the accumulators start at zero.  acc_is_zero is the caller's promise that
+// they already are (include/g2s.h), and then nothing is cleared.
+//   deterministic mode   float atomics would make the sums depend on the order the waves finish in: `fix` becomes the
+//                        256-aligned start of `workspace`, which must hold `need` bytes (`sizer`_workspace_bytes is
+//                        the query that says so) and takes the targets' sums back to back as 2^-40 fixed point;
+//   default mode         `fix` is NULL and the targets themselves are the accumulators.
+static int scatter_begin(const char *sizer, size_t need, void *workspace, size_t workspace_bytes, int acc_is_zero,
+                         hipStream_t st, const ScatterTarget *targets, int n_targets, long long *&fix) {
+    fix = nullptr;
+    if (deterministic()) {
+        if (!workspace || workspace_bytes < need)
+            return fail(G2S_ERR_WORKSPACE, "deterministic mode: the backward needs its fixed-point workspace "
+                        "(%s_workspace_bytes = %zu bytes, got %zu)", sizer, need,
+                        workspace ? workspace_bytes : (size_t)0);
+        fix = reinterpret_cast<long long *>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+        size_t total = 0;
+        for (int k = 0; k < n_targets; k++) total += targets[k].n;
+        if (!acc_is_zero && hipMemsetAsync(fix, 0, total * sizeof(long long), st) != hipSuccess)
+            return fail(G2S_ERR_LAUNCH, "hipMemsetAsync(workspace) failed");
+    } else if (!acc_is_zero) {
+        for (int k = 0; k < n_targets; k++)
+            if (targets[k].ptr && hipMemsetAsync(targets[k].ptr, 0, targets[k].n * sizeof(float), st) != hipSuccess)
+                return fail(G2S_ERR_LAUNCH, "hipMemsetAsync(%s) failed", targets[k].name);
+    }
     return G2S_OK;
 }
 

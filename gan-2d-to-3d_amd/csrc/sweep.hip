@@ -11,7 +11,8 @@
 //                           twelve pose values of a frame are wave-uniform loads.  Grid (floats / W / 256, V /
 //                           SWEEP_VPB, B): the frames of an image are spread over the grid so that B = 1 fills the
 //                           device too, the re-read of the vertices by the other frame groups hits L2.
-//   sweep_shade_kernel      one thread per output pixel, as raster_rgb_kernel: per supersample the winner's three
+//   sweep_shade_kernel      one thread per output pixel, as raster_rgb_kernel (the same resolve_pixel and
+//                           persp_weights of shade_core.h, the same winner_verts): per supersample the winner's three
 //                           vertices, perspective-correct weights u_k = w_k D / z_k (D = 1 / sum w_k / z_k, z of the
 //                           POSED vertices; no clamp, no renormalisation), attribute and normal gathered at the
 //                           vertices from the maps of image b = f / V (a few hundred KB, resident in L2 for all V
@@ -31,6 +32,7 @@
 // No backward: nothing here carries a gradient.
 #include "g2s_common.h"
 #include "raster_core.h"
+#include "shade_core.h"
 
 namespace g2s {
 
@@ -112,27 +114,15 @@ __device__ __forceinline__ bool shade_sample(const ShadeParams &p, int f, int b,
         for (int c = 0; c < p.Cout; c++) col[c] = p.bg[c];
         return false;
     }
-    const int g = fn % p.F;
-    const bool rev = p.fill_back && fn >= p.F;
-    int v[3];
-    if (IMPLICIT) {
-        implicit_face(g, p.S, v);
-    } else {
-        v[0] = p.faces[3 * g];
-        v[1] = p.faces[3 * g + 1];
-        v[2] = p.faces[3 * g + 2];
-    }
-    if (rev) {
-        const int t = v[0];
-        v[0] = v[2];
-        v[2] = t;
-    }
-    float w[3], z[3], u[3];
+    int g, v[3];
+    bool rev;
+    winner_verts(fn, p.F, p.S, IMPLICIT ? nullptr : p.faces, p.fill_back, g, rev, v);
+    float w[3], z[3], wz[3], u[3];
     for (int k = 0; k < 3; k++) {
         w[k] = p.bary[3 * si + k];
         z[k] = p.verts[((size_t)f * p.N + v[k]) * 3 + 2];
     }
-    const float depth = 1.0f / (w[0] / z[0] + w[1] / z[1] + w[2] / z[2]);
+    const float depth = persp_weights(w, z, wz);
     for (int k = 0; k < 3; k++) u[k] = w[k] * depth / z[k];
     float a[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (MODE == 0 || MODE == 1) {
@@ -174,21 +164,9 @@ template <bool IMPLICIT, int MODE>
 __global__ __launch_bounds__(256) void sweep_shade_kernel(ShadeParams p) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)p.B * p.V * p.S * p.S) return;
-    const int f = (int)(i / ((long)p.S * p.S));
-    const int b = f / p.V;
-    const int r = (int)((i / p.S) % p.S), c0 = (int)(i % p.S);
-    float sum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    int covered = 0;
-    for (int dy = 0; dy < p.ssaa; dy++)
-        for (int dx = 0; dx < p.ssaa; dx++) {
-            const int yi = p.is - 1 - (r * p.ssaa + dy);   // row of the (unflipped) raster
-            float col[4];
-            if (shade_sample<IMPLICIT, MODE>(p, f, b, yi, c0 * p.ssaa + dx, col)) covered++;
-            for (int c = 0; c < p.Cout; c++) sum[c] += col[c];
-        }
-    const float inv = 1.0f / (float)(p.ssaa * p.ssaa);
-    for (int c = 0; c < p.Cout; c++) p.out[(((size_t)f * p.Cout + c) * p.S + r) * p.S + c0] = sum[c] * inv;
-    if (p.alpha) p.alpha[((size_t)f * p.S + r) * p.S + c0] = (float)covered * inv;
+    resolve_pixel(i, p.S, p.ssaa, p.Cout, p.out, p.alpha, [&](int f, int yi, int xi, float col[4]) {
+        return shade_sample<IMPLICIT, MODE>(p, f, f / p.V, yi, xi, col);
+    });
 }
 
 template <bool IMPLICIT>

@@ -42,6 +42,45 @@ def _workspace(device, nbytes):
     return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
+def _rasterise(verts, faces, F, K, orig_size, S, ssaa, fill_back, near, far, maps=True):
+    """g2s_raster_depth_fwd over verts (B,N,3) contiguous; `faces` (F,3) int32 or None (implicit grid); K the nine
+    host floats.  Returns (depth (B,S,S), face_idx (B,is,is), bary (B,is,is,3)), is = S * ssaa; without `maps` the
+    two saved maps are None and the kernel does not write them."""
+    B, N, _ = verts.shape
+    L = _lib.load()
+    dev = verts.device
+    depth = torch.empty((B, S, S), dtype=torch.float32, device=dev)
+    fidx = torch.empty((B, S * ssaa, S * ssaa), dtype=torch.int32, device=dev) if maps else None
+    bary = torch.empty((B, S * ssaa, S * ssaa, 3), dtype=torch.float32, device=dev) if maps else None
+    ws = _workspace(dev, L.g2s_raster_workspace_bytes(B, N, F, S))
+    _lib.check(L.g2s_raster_depth_fwd(_lib.ptr(verts), _lib.ptr(faces), B, N, F, S, (_lib.C.c_float * 9)(*K),
+                                      float(orig_size), ssaa, int(bool(fill_back)), float(near), float(far),
+                                      _lib.ptr(depth), _lib.ptr(fidx), _lib.ptr(bary), _lib.ptr(ws), ws.numel(),
+                                      _lib.stream()))
+    return depth, fidx, bary
+
+
+def _scatter_targets(shapes, ws_bytes, device):
+    """Where a backward scatters into: one float32 tensor per entry of `shapes` (None = that gradient is not
+    wanted -> None) -> (targets, workspace, workspace bytes, acc_is_zero).  Whatever the kernels accumulate in
+    must start at zero: in default mode the targets themselves, in deterministic mode the fixed-point workspace of
+    `ws_bytes()` bytes (include/g2s.h).  It is a slice of the step's cleared pool when there is one (acc_is_zero =
+    1), else the call clears it with a memset of its own.  One flag covers every target: if any of them missed the
+    pool, all are allocated uncleared and the call clears them, rather than split the call."""
+    def fresh():
+        return [None if s is None else torch.empty(s, dtype=torch.float32, device=device) for s in shapes]
+    if _lib.load().g2s_get_deterministic():
+        nbytes = ws_bytes()
+        ws = _zp.take(((nbytes + 3) // 4,), device)
+        pre = ws is not None
+        if ws is None:
+            ws = _workspace(device, nbytes)
+        return fresh(), ws, nbytes, int(pre)
+    targets = [None if s is None else _zp.take(tuple(s), device) for s in shapes]
+    pre = all(t is not None for s, t in zip(shapes, targets) if s is not None)
+    return (targets if pre else fresh()), None, 0, int(pre)
+
+
 def _regular_grid_faces(S, device):
     key = (S, device)
     f = _regular_grid_faces.cache.get(key)
@@ -72,19 +111,7 @@ class RenderDepthFunction(Function):
         ssaa = 2 if anti_aliasing else 1
         F = 2 * (S - 1) * (S - 1) if faces is None else faces.shape[0]
         need_grad = ctx.needs_input_grad[0]
-        L = _lib.load()
-        depth = torch.empty((B, S, S), dtype=torch.float32, device=verts.device)
-        fidx = bary = None
-        if need_grad:
-            fidx = torch.empty((B, S * ssaa, S * ssaa), dtype=torch.int32, device=verts.device)
-            bary = torch.empty((B, S * ssaa, S * ssaa, 3), dtype=torch.float32, device=verts.device)
-        ws_bytes = L.g2s_raster_workspace_bytes(B, N, F, S)
-        ws = _workspace(verts.device, ws_bytes)
-        Kc = (_lib.C.c_float * 9)(*K)
-        _lib.check(L.g2s_raster_depth_fwd(_lib.ptr(verts), _lib.ptr(faces), B, N, F, S, Kc,
-                                          float(orig_size), ssaa, int(bool(fill_back)),
-                                          float(near), float(far), _lib.ptr(depth), _lib.ptr(fidx),
-                                          _lib.ptr(bary), _lib.ptr(ws), ws.numel(), _lib.stream()))
+        depth, fidx, bary = _rasterise(verts, faces, F, K, orig_size, S, ssaa, fill_back, near, far, maps=need_grad)
         if need_grad:
             ctx.save_for_backward(verts, faces, fidx, bary)
         ctx.meta = (K, float(orig_size), S, ssaa, F)
@@ -98,25 +125,11 @@ class RenderDepthFunction(Function):
         g = grad_depth.contiguous().float()
         L = _lib.load()
         Kc = (_lib.C.c_float * 9)(*K)
-        # the scatter target must start at zero — default mode: the gradient itself; deterministic mode: the
-        # fixed-point scratch buffer (include/g2s.h).  A slice of the step's cleared pool when there is one
-        # (the call is then told so, acc_is_zero = 1), else the call clears it with a memset of its own.
-        ws, ws_bytes, pre = None, 0, False
-        if L.g2s_get_deterministic():
-            ws_bytes = L.g2s_raster_bwd_workspace_bytes(B, N)
-            ws = _zp.take(((ws_bytes + 3) // 4,), verts.device)
-            pre = ws is not None
-            if ws is None:
-                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=verts.device)
-            gv = torch.empty_like(verts)
-        else:
-            gv = _zp.take(tuple(verts.shape), verts.device)
-            pre = gv is not None
-            if gv is None:
-                gv = torch.empty_like(verts)
+        (gv,), ws, ws_bytes, pre = _scatter_targets([verts.shape], lambda: L.g2s_raster_bwd_workspace_bytes(B, N),
+                                                    verts.device)
         _lib.check(L.g2s_raster_depth_bwd_ex(_lib.ptr(verts), _lib.ptr(faces), _lib.ptr(g),
                                              _lib.ptr(fidx), _lib.ptr(bary), B, N, F, S, Kc, orig_size,
-                                             ssaa, _lib.ptr(gv), _lib.ptr(ws), ws_bytes, int(pre), _lib.stream()))
+                                             ssaa, _lib.ptr(gv), _lib.ptr(ws), ws_bytes, pre, _lib.stream()))
         return gv, None, None, None, None, None, None, None, None
 
 
@@ -136,15 +149,7 @@ class RenderRgbFunction(Function):
         ssaa = 2 if anti_aliasing else 1
         F, ts, C = tex.shape[1], tex.shape[2], tex.shape[5]
         L = _lib.load()
-        depth = torch.empty((B, S, S), dtype=torch.float32, device=verts.device)
-        fidx = torch.empty((B, S * ssaa, S * ssaa), dtype=torch.int32, device=verts.device)
-        bary = torch.empty((B, S * ssaa, S * ssaa, 3), dtype=torch.float32, device=verts.device)
-        ws = _workspace(verts.device, L.g2s_raster_workspace_bytes(B, N, F, S))
-        Kc = (_lib.C.c_float * 9)(*K)
-        _lib.check(L.g2s_raster_depth_fwd(_lib.ptr(verts), _lib.ptr(faces), B, N, F, S, Kc, float(orig_size), ssaa,
-                                          int(bool(fill_back)), float(near), float(far),
-                                          _lib.ptr(depth), _lib.ptr(fidx), _lib.ptr(bary), _lib.ptr(ws),
-                                          ws.numel(), _lib.stream()))
+        _, fidx, bary = _rasterise(verts, faces, F, K, orig_size, S, ssaa, fill_back, near, far)
         rgb = torch.empty((B, C, S, S), dtype=torch.float32, device=verts.device)
         _lib.check(L.g2s_raster_rgb_fwd(_lib.ptr(verts), _lib.ptr(faces), _lib.ptr(fidx), _lib.ptr(bary), _lib.ptr(tex),
                                         B, N, F, S, ssaa, ts, C, (_lib.C.c_float * C)(*background),
@@ -164,27 +169,12 @@ class RenderRgbFunction(Function):
         g = grad_rgb.contiguous().float()
         L = _lib.load()
         Kc = (_lib.C.c_float * 9)(*K)
-        # the scatter targets must start at zero, as in RenderDepthFunction.backward: slices of the step's
-        # cleared pool when there is one (acc_is_zero = 1), else the call clears them itself
-        ws, ws_bytes, gv, gt = None, 0, None, None
-        if L.g2s_get_deterministic():
-            ws_bytes = L.g2s_raster_rgb_bwd_workspace_bytes(B, N, F, ts, C)
-            ws = _zp.take(((ws_bytes + 3) // 4,), verts.device)
-            pre = ws is not None
-            if ws is None:
-                ws = _workspace(verts.device, ws_bytes)
-            gv = torch.empty_like(verts) if want_v else None
-            gt = torch.empty_like(tex) if want_t else None
-        else:
-            gv = _zp.take(tuple(verts.shape), verts.device) if want_v else None
-            gt = _zp.take(tuple(tex.shape), verts.device) if want_t else None
-            pre = (gv is not None or not want_v) and (gt is not None or not want_t)
-            if not pre:     # one flag covers both targets: clear the pooled one again rather than split the call
-                gv = torch.empty_like(verts) if want_v else None
-                gt = torch.empty_like(tex) if want_t else None
+        (gv, gt), ws, ws_bytes, pre = _scatter_targets(
+            [verts.shape if want_v else None, tex.shape if want_t else None],
+            lambda: L.g2s_raster_rgb_bwd_workspace_bytes(B, N, F, ts, C), verts.device)
         _lib.check(L.g2s_raster_rgb_bwd(_lib.ptr(verts), _lib.ptr(faces), _lib.ptr(fidx), _lib.ptr(bary),
                                         _lib.ptr(tex), _lib.ptr(g), B, N, F, S, Kc, orig_size, ssaa, ts, C, eps,
-                                        _lib.ptr(gt), _lib.ptr(gv), _lib.ptr(ws), ws_bytes, int(pre), _lib.stream()))
+                                        _lib.ptr(gt), _lib.ptr(gv), _lib.ptr(ws), ws_bytes, pre, _lib.stream()))
         return gv, gt, None, None, None, None, None, None, None, None, None, None
 
 
@@ -208,14 +198,7 @@ class RenderFunction(Function):
         fb = int(bool(fill_back))
         L = _lib.load()
         st = _lib.stream()
-        depth = torch.empty((B, S, S), dtype=torch.float32, device=verts.device)
-        fidx = torch.empty((B, S * ssaa, S * ssaa), dtype=torch.int32, device=verts.device)
-        bary = torch.empty((B, S * ssaa, S * ssaa, 3), dtype=torch.float32, device=verts.device)
-        ws = _workspace(verts.device, L.g2s_raster_workspace_bytes(B, N, F, S))
-        Kc = (_lib.C.c_float * 9)(*K)
-        _lib.check(L.g2s_raster_depth_fwd(_lib.ptr(verts), _lib.ptr(faces), B, N, F, S, Kc, float(orig_size), ssaa,
-                                          fb, float(near), float(far), _lib.ptr(depth), _lib.ptr(fidx),
-                                          _lib.ptr(bary), _lib.ptr(ws), ws.numel(), st))
+        depth, fidx, bary = _rasterise(verts, faces, F, K, orig_size, S, ssaa, fb, near, far)
         lit = None
         if light is not None:
             lit = torch.empty((B, F * (1 + fb), 3), dtype=torch.float32, device=verts.device)
@@ -245,62 +228,32 @@ class RenderFunction(Function):
         L = _lib.load()
         st = _lib.stream()
         Kc = (_lib.C.c_float * 9)(*K)
-        det = bool(L.g2s_get_deterministic())
         dev = verts.device
         gv = gt = None
-        # every scatter target must start at zero, as in the two Functions above: slices of the step's cleared
-        # pool when there is one (acc_is_zero = 1), else the call clears them itself
         if want_v and grad_depth is not None:
             g = grad_depth.contiguous().float()
-            ws, ws_bytes = None, 0
-            if det:
-                ws_bytes = L.g2s_raster_bwd_workspace_bytes(B, N)
-                ws = _zp.take(((ws_bytes + 3) // 4,), dev)
-                pre = ws is not None
-                if ws is None:
-                    ws = _workspace(dev, ws_bytes)
-                gv = torch.empty_like(verts)
-            else:
-                gv = _zp.take(tuple(verts.shape), dev)
-                pre = gv is not None
-                if gv is None:
-                    gv = torch.empty_like(verts)
+            (gv,), ws, ws_bytes, pre = _scatter_targets([verts.shape], lambda: L.g2s_raster_bwd_workspace_bytes(B, N),
+                                                        dev)
             _lib.check(L.g2s_raster_depth_bwd_ex(_lib.ptr(verts), _lib.ptr(faces), _lib.ptr(g), _lib.ptr(fidx),
                                                  _lib.ptr(bary), B, N, F, S, Kc, orig_size, ssaa, _lib.ptr(gv),
-                                                 _lib.ptr(ws), ws_bytes, int(pre), st))
+                                                 _lib.ptr(ws), ws_bytes, pre, st))
         if grad_rgb is not None and (want_v or want_t):
             g = grad_rgb.contiguous().float()
             # the light moves with the vertices only through its directional term
             want_l = want_v and lit is not None and any(float(x) != 0.0 for x in light[1])
-            lshape = (B, F * (1 + fb), 3)
-            ws, ws_bytes, gc, gl = None, 0, None, None
-            if det:
-                ws_bytes = L.g2s_raster_rgba_bwd_workspace_bytes(B, N, F, ts, C, fb)
-                ws = _zp.take(((ws_bytes + 3) // 4,), dev)
-                pre = ws is not None
-                if ws is None:
-                    ws = _workspace(dev, ws_bytes)
-                gc = torch.empty_like(verts) if want_v else None
-                gt = torch.empty_like(tex) if want_t else None
-                gl = torch.empty(lshape, dtype=torch.float32, device=dev) if want_l else None
-            else:
-                gc = _zp.take(tuple(verts.shape), dev) if want_v else None
-                gt = _zp.take(tuple(tex.shape), dev) if want_t else None
-                gl = _zp.take(lshape, dev) if want_l else None
-                pre = (gc is not None or not want_v) and (gt is not None or not want_t) and (gl is not None or not want_l)
-                if not pre:     # one flag covers the three targets, as in RenderRgbFunction.backward
-                    gc = torch.empty_like(verts) if want_v else None
-                    gt = torch.empty_like(tex) if want_t else None
-                    gl = torch.empty(lshape, dtype=torch.float32, device=dev) if want_l else None
+            (gc, gt, gl), ws, ws_bytes, pre = _scatter_targets(
+                [verts.shape if want_v else None, tex.shape if want_t else None,
+                 (B, F * (1 + fb), 3) if want_l else None],
+                lambda: L.g2s_raster_rgba_bwd_workspace_bytes(B, N, F, ts, C, fb), dev)
             _lib.check(L.g2s_raster_rgba_bwd(_lib.ptr(verts), _lib.ptr(faces), _lib.ptr(fidx), _lib.ptr(bary),
                                              _lib.ptr(tex), _lib.ptr(lit), _lib.ptr(g), B, N, F, S, Kc, orig_size,
                                              ssaa, ts, C, fb, eps, _lib.ptr(gt), _lib.ptr(gc), _lib.ptr(gl),
-                                             _lib.ptr(ws), ws_bytes, int(pre), st))
+                                             _lib.ptr(ws), ws_bytes, pre, st))
             if want_l:
                 # added to the texture path's camera-space gradient (acc_is_zero = 1: nothing is cleared); the
                 # fixed-point sums of deterministic mode need a cleared workspace of their own
                 ws, ws_bytes = None, 0
-                if det:
+                if L.g2s_get_deterministic():
                     ws_bytes = L.g2s_raster_bwd_workspace_bytes(B, N)
                     ws = _zp.zeros(((ws_bytes + 3) // 4,), dev)
                 f3 = _lib.C.c_float * 3
@@ -352,7 +305,10 @@ class Renderer:
             self._K_host = (key, tuple(k[0].reshape(9).cpu().tolist()))
         return self._K_host[1]
 
-    def render_depth(self, vertices, faces, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
+    def _camera(self, vertices, K, R, t, dist_coeffs, orig_size):
+        """The camera of one call: K, R, t, dist_coeffs and orig_size default to the constructor's; lens distortion
+        is refused, before anything touches the device.  Returns (vertices in camera space, the nine host floats of
+        K, orig_size)."""
         K = self.K if K is None else K
         R = self.R if R is None else R
         t = self.t if t is None else t
@@ -362,18 +318,21 @@ class Renderer:
             raise NotImplementedError("lens distortion is not supported (GAN2Shape never sets it)")
         if K is None:
             raise ValueError("camera_mode='projection' needs K")
-        # R, t: identity / zero at GAN2Shape's call site (renderer.py:30-34); applied on the host
-        # side otherwise so that the kernel keeps the R = I, t = 0 form.
+        # R, t: identity / zero at GAN2Shape's call site (renderer.py:30-34); applied as torch ops
+        # otherwise so that the kernel keeps the R = I, t = 0 form and autograd carries them.
         if self._needs_transform(R, t):
             if R is not None:
                 vertices = torch.matmul(vertices, R.reshape(-1, 3, 3).transpose(2, 1))
             if t is not None:
                 vertices = vertices + t.reshape(-1, 1, 3)
+        return vertices, self._host_K(K), orig_size
+
+    def render_depth(self, vertices, faces, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
+        vertices, K9, orig_size = self._camera(vertices, K, R, t, dist_coeffs, orig_size)
         S = self.image_size
         f = self._shared_faces(faces, vertices.shape[1], S)
-        return RenderDepthFunction.apply(vertices, f, self._host_K(K), orig_size, S,
-                                         self.anti_aliasing, self.fill_back, DEFAULT_NEAR,
-                                         DEFAULT_FAR)
+        return RenderDepthFunction.apply(vertices, f, K9, orig_size, S, self.anti_aliasing, self.fill_back,
+                                         DEFAULT_NEAR, DEFAULT_FAR)
 
     def _needs_transform(self, R, t):
         key = tuple(None if x is None else (x.data_ptr(), x._version) for x in (R, t))
@@ -425,22 +384,11 @@ class Renderer:
 
     def _texture_args(self, vertices, faces, textures, K, R, t, dist_coeffs, orig_size):
         """Argument checks and the positional arguments that RenderRgbFunction and RenderFunction share."""
-        K = self.K if K is None else K
-        R = self.R if R is None else R
-        t = self.t if t is None else t
-        orig_size = self.orig_size if orig_size is None else orig_size
         light = self._light()
         if light is not None and textures.shape[-1] != 3:
             raise ValueError(f"lighting needs 3 colour channels, got textures with C = {textures.shape[-1]}")
-        if K is None:
-            raise ValueError("camera_mode='projection' needs K")
+        vertices, K9, orig_size = self._camera(vertices.float(), K, R, t, dist_coeffs, orig_size)
         _lib.require_cuda(vertices, textures)
-        vertices = vertices.float()
-        if self._needs_transform(R, t):
-            if R is not None:
-                vertices = torch.matmul(vertices, R.reshape(-1, 3, 3).transpose(2, 1))
-            if t is not None:
-                vertices = vertices + t.reshape(-1, 1, 3)
         B, N, _ = vertices.shape
         S = self.image_size
         f = self._shared_faces(faces, N, S)
@@ -453,13 +401,8 @@ class Renderer:
             tex = tex * float(self.light_intensity_ambient)
         bg = [float(v) for v in self.background_color][:C]
         bg += [bg[-1]] * (C - len(bg))
-        return (vertices, tex, f, self._host_K(K), orig_size, S, self.anti_aliasing, self.fill_back, self.near,
+        return (vertices, tex, f, K9, orig_size, S, self.anti_aliasing, self.fill_back, self.near,
                 self.far, tuple(bg), self.rasterizer_eps), light
-
-    def _no_distortion(self, dist_coeffs):
-        dist_coeffs = self.dist_coeffs if dist_coeffs is None else dist_coeffs
-        if dist_coeffs is not None and bool((dist_coeffs != 0).any()):
-            raise NotImplementedError("lens distortion is not supported (GAN2Shape never sets it)")
 
     def render_rgb(self, vertices, faces, textures, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
         """[B, C, S, S] image of the textured mesh: rasterize with the constructor's near / far
@@ -484,45 +427,23 @@ class Renderer:
         far); alpha = the share of a pixel's 2x2 samples that a face covers.  rgb and depth are differentiable
         w.r.t. `vertices` (and rgb w.r.t. `textures`); ALPHA HAS NO GRADIENT: the package's silhouette-edge
         heuristic is not rebuilt (nothing pins it)."""
-        self._no_distortion(dist_coeffs)
         args, light = self._texture_args(vertices, faces, textures, K, R, t, dist_coeffs, orig_size)
         return RenderFunction.apply(*args, light)
 
     def render_silhouettes(self, vertices, faces, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
         """alpha [B, S, S] of `render`, from one rasterization and no texture pass.  NO GRADIENT (see `render`)."""
-        K = self.K if K is None else K
-        R = self.R if R is None else R
-        t = self.t if t is None else t
-        orig_size = self.orig_size if orig_size is None else orig_size
-        self._no_distortion(dist_coeffs)
-        if K is None:
-            raise ValueError("camera_mode='projection' needs K")
-        _lib.require_cuda(vertices)
         with torch.no_grad():
-            verts = vertices.float()
-            if self._needs_transform(R, t):
-                if R is not None:
-                    verts = torch.matmul(verts, R.reshape(-1, 3, 3).transpose(2, 1))
-                if t is not None:
-                    verts = verts + t.reshape(-1, 1, 3)
+            verts, K9, orig_size = self._camera(vertices.float(), K, R, t, dist_coeffs, orig_size)
+            _lib.require_cuda(verts)
             verts = verts.contiguous()
             B, N, _ = verts.shape
             S = self.image_size
             f = self._shared_faces(faces, N, S)
             F = 2 * (S - 1) * (S - 1) if f is None else f.shape[0]
             ssaa = 2 if self.anti_aliasing else 1
-            L = _lib.load()
-            depth = torch.empty((B, S, S), dtype=torch.float32, device=verts.device)
-            fidx = torch.empty((B, S * ssaa, S * ssaa), dtype=torch.int32, device=verts.device)
-            bary = torch.empty((B, S * ssaa, S * ssaa, 3), dtype=torch.float32, device=verts.device)
-            ws = _workspace(verts.device, L.g2s_raster_workspace_bytes(B, N, F, S))
-            Kc = (_lib.C.c_float * 9)(*self._host_K(K))
-            _lib.check(L.g2s_raster_depth_fwd(_lib.ptr(verts), _lib.ptr(f), B, N, F, S, Kc, float(orig_size), ssaa,
-                                              int(bool(self.fill_back)), float(self.near), float(self.far),
-                                              _lib.ptr(depth), _lib.ptr(fidx), _lib.ptr(bary), _lib.ptr(ws),
-                                              ws.numel(), _lib.stream()))
+            _, fidx, _ = _rasterise(verts, f, F, K9, orig_size, S, ssaa, self.fill_back, self.near, self.far)
             alpha = torch.empty((B, S, S), dtype=torch.float32, device=verts.device)
-            _lib.check(L.g2s_raster_rgba_fwd(None, None, _lib.ptr(fidx), None, None, None, B, N, F, S, ssaa, 1, 1,
+            _lib.check(_lib.load().g2s_raster_rgba_fwd(None, None, _lib.ptr(fidx), None, None, None, B, N, F, S, ssaa, 1, 1,
                                              int(bool(self.fill_back)), None, 0.0, None, _lib.ptr(alpha),
                                              _lib.stream()))
         return alpha
@@ -598,14 +519,7 @@ def sweep_frames(verts, pose, faces, attr, normal, light, K, orig_size, image_si
         dev = verts.device
         posed = torch.empty((B * V, N, 3), dtype=torch.float32, device=dev)
         _lib.check(L.g2s_sweep_verts(_lib.ptr(verts), _lib.ptr(pose), _lib.ptr(posed), B, V, N, st))
-        depth = torch.empty((B * V, S, S), dtype=torch.float32, device=dev)
-        fidx = torch.empty((B * V, S * ssaa, S * ssaa), dtype=torch.int32, device=dev)
-        bary = torch.empty((B * V, S * ssaa, S * ssaa, 3), dtype=torch.float32, device=dev)
-        ws = _workspace(dev, L.g2s_raster_workspace_bytes(B * V, N, F, S))
-        Kc = (_lib.C.c_float * 9)(*K)
-        _lib.check(L.g2s_raster_depth_fwd(_lib.ptr(posed), _lib.ptr(faces), B * V, N, F, S, Kc, float(orig_size), ssaa,
-                                          fb, float(near), float(far), _lib.ptr(depth), _lib.ptr(fidx),
-                                          _lib.ptr(bary), _lib.ptr(ws), ws.numel(), st))
+        depth, fidx, bary = _rasterise(posed, faces, F, K, orig_size, S, ssaa, fb, near, far)
         rgb = torch.empty((B, V, Cout, S, S), dtype=torch.float32, device=dev)
         alpha = torch.empty((B, V, S, S), dtype=torch.float32, device=dev) if want_alpha else None
         _lib.check(L.g2s_sweep_shade(_lib.ptr(posed), _lib.ptr(faces), _lib.ptr(fidx), _lib.ptr(bary), _lib.ptr(attr),
@@ -637,12 +551,8 @@ def pseudo_frames(verts, pose, rays, K, albedo, normal, light, mask, depth_lo, d
         dev = verts.device
         posed = torch.empty((B * V, N, 3), dtype=torch.float32, device=dev)
         _lib.check(L.g2s_sweep_verts(_lib.ptr(verts), _lib.ptr(pose), _lib.ptr(posed), B, V, N, st))
-        warped = torch.empty((B * V, S, S), dtype=torch.float32, device=dev)
-        ws = _workspace(dev, L.g2s_raster_workspace_bytes(B * V, N, F, S))
+        warped, _, _ = _rasterise(posed, None, F, K, orig_size, S, ssaa, fill_back, DEFAULT_NEAR, DEFAULT_FAR, maps=False)
         Kc = (_lib.C.c_float * 9)(*K)
-        _lib.check(L.g2s_raster_depth_fwd(_lib.ptr(posed), None, B * V, N, F, S, Kc, float(orig_size), ssaa,
-                                          int(bool(fill_back)), DEFAULT_NEAR, DEFAULT_FAR, _lib.ptr(warped), None, None,
-                                          _lib.ptr(ws), ws.numel(), st))
         im = torch.empty((B, V, C, S, S), dtype=torch.float32, device=dev)
         mout = torch.empty((B, V, S, S), dtype=torch.float32, device=dev) if want_mask else None
         _lib.check(L.g2s_sweep_pseudo(_lib.ptr(warped), _lib.ptr(rays), _lib.ptr(pose), Kc, _lib.ptr(albedo),

@@ -323,27 +323,11 @@ class Renderer():
             ssaa = 2 if r.anti_aliasing else 1
             bc, vc = sweep_chunks(b, V, max_frames, (S * ssaa) ** 2 * 16 + h * w * 12)
             K = r._host_K(r.K)
-            out = alpha = dmap = None
-            for b0 in range(0, b, bc):
-                for v0 in range(0, V, vc):
-                    sb, sv = slice(b0, b0 + bc), slice(v0, v0 + vc)
-                    rgb_c, alpha_c, depth_c = nr.sweep_frames(
-                        verts[sb], pose[sb, sv], faces, im[sb], None if normal is None else normal[sb],
-                        None if light is None else light[sb, sv].reshape(-1, 5), K, r.orig_size, S,
-                        r.anti_aliasing, r.fill_back, r.near, r.far, bg, grey, m, return_alpha, return_depth)
-                    if bc >= b and vc >= V:
-                        out, alpha, dmap = rgb_c, alpha_c, depth_c
-                        break
-                    if out is None:
-                        out = torch.empty((b, V) + tuple(rgb_c.shape[2:]), dtype=torch.float32, device=dev)
-                        alpha = torch.empty((b, V, S, S), dtype=torch.float32, device=dev) if return_alpha else None
-                        dmap = torch.empty((b, V, S, S), dtype=torch.float32, device=dev) if return_depth else None
-                    out[sb, sv] = rgb_c
-                    if return_alpha:
-                        alpha[sb, sv] = alpha_c
-                    if return_depth:
-                        dmap[sb, sv] = depth_c
-        result = (out,) + ((alpha,) if return_alpha else ()) + ((dmap,) if return_depth else ())
+            result = sweep_assemble(b, V, bc, vc, lambda sb, sv: nr.sweep_frames(
+                verts[sb], pose[sb, sv], faces, im[sb], None if normal is None else normal[sb],
+                None if light is None else light[sb, sv].reshape(-1, 5), K, r.orig_size, S,
+                r.anti_aliasing, r.fill_back, r.near, r.far, bg, grey, m, return_alpha, return_depth))
+        result = tuple(x for x in result if x is not None)     # rgb, then alpha and depth where asked for
         return result[0] if len(result) == 1 else result
 
     def pseudo_pose(self, views, base_view=None, b=1):
@@ -414,23 +398,10 @@ class Renderer():
             verts = (rays.unsqueeze(0) * depth.float().reshape(b, -1, 1)).contiguous()
             pose = self.pseudo_pose(views, base_view, b)
             K = self._K9
-            out = mout = None
-            for b0 in range(0, b, bc):
-                for v0 in range(0, V, vc):
-                    sb, sv = slice(b0, b0 + bc), slice(v0, v0 + vc)
-                    im_c, m_c = nr.pseudo_frames(
-                        verts[sb], pose[sb, sv], rays, K, albedo[sb], None if lights is None else normal[sb],
-                        None if lights is None else lights[sb, sv].reshape(-1, 4), None if mask is None else mask[sb],
-                        self.min_depth - margin, self.max_depth + margin, r.orig_size, S, r.anti_aliasing,
-                        r.fill_back)
-                    if bc >= b and vc >= V:
-                        out, mout = im_c, m_c
-                        break
-                    if out is None:
-                        out = torch.empty((b, V, c, S, S), dtype=torch.float32, device=dev)
-                        mout = torch.empty((b, V, S, S), dtype=torch.float32, device=dev)
-                    out[sb, sv] = im_c
-                    mout[sb, sv] = m_c
+            out, mout = sweep_assemble(b, V, bc, vc, lambda sb, sv: nr.pseudo_frames(
+                verts[sb], pose[sb, sv], rays, K, albedo[sb], None if lights is None else normal[sb],
+                None if lights is None else lights[sb, sv].reshape(-1, 4), None if mask is None else mask[sb],
+                self.min_depth - margin, self.max_depth + margin, r.orig_size, S, r.anti_aliasing, r.fill_back))
         return out, mout.unsqueeze(2)
 
     def render_given_view(self, im, depth, view, mask=None, grid_sample=True):
@@ -467,6 +438,26 @@ def sweep_chunks(b, V, max_frames, bytes_per_frame, budget=256 << 20):
         raise ValueError("max_frames must be at least 1")
     bc = min(b, max_frames)
     return bc, min(V, max(1, max_frames // bc))
+
+
+def sweep_assemble(b, V, bc, vc, run):
+    """The (b, V, ...) results of a sweep from its chunks of bc images x vc frames: run(sb, sv) renders the chunk
+    of the image slice sb and the frame slice sv and returns a tuple of (len sb, len sv, ...) tensors, or None where
+    a result is not wanted.  A single chunk's tensors are returned as they are, without a copy."""
+    outs = None
+    for b0 in range(0, b, bc):
+        for v0 in range(0, V, vc):
+            sb, sv = slice(b0, b0 + bc), slice(v0, v0 + vc)
+            parts = run(sb, sv)
+            if bc >= b and vc >= V:
+                return parts
+            if outs is None:
+                outs = [None if p is None else torch.empty((b, V) + tuple(p.shape[2:]), dtype=p.dtype, device=p.device)
+                        for p in parts]
+            for o, p in zip(outs, parts):
+                if o is not None:
+                    o[sb, sv] = p
+    return tuple(outs)
 
 
 def compose_sweep_pose(rotations, v_before, v_after, rot_center_depth, b=1):

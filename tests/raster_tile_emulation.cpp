@@ -9,6 +9,7 @@
 #include <cstring>
 #include <vector>
 #include "../gan-2d-to-3d_amd/csrc/raster_core.h"
+#include "../gan-2d-to-3d_amd/csrc/shade_core.h"
 
 using namespace g2s;
 
@@ -139,7 +140,45 @@ extern "C" int g2s_emul_render_depth(const float *verts, const int *faces, int B
     return 0;
 }
 
-// backward: same per-sample arithmetic as raster_bwd_samples + raster_bwd_project (serial adds).
+// winner_verts as every pass that reads the maps calls it: ids 0 .. n-1 -> g[n], rev[n], v[n][3].
+extern "C" void g2s_emul_winner_verts(int n, int F, int S, const int *faces, int reversible, int *g, int *rev, int *v) {
+    for (int fn = 0; fn < n; fn++) {
+        bool r;
+        winner_verts(fn, F, S, faces, reversible != 0, g[fn], r, v + 3 * fn);
+        rev[fn] = r;
+    }
+}
+
+// Forward of the texture pass (raster_rgb_kernel without light): the sample colour of raster_rgb.hip written with
+// the functions of shade_core.h it is written with there, resolved by the same resolve_pixel.
+extern "C" int g2s_emul_render_rgb(const float *verts, const int *faces, const int *face_idx, const float *bary,
+                                   const float *tex, int B, int N, int F, int S, int ssaa, int ts, int C,
+                                   const float *background, float eps, float *rgb, float *alpha) {
+    const int is = S * ssaa;
+    auto sample = [&](int b, int yi, int xi, float col[4]) {
+        const size_t si = ((size_t)b * is + yi) * is + xi;
+        const int fn = face_idx[si];
+        if (fn < 0) {
+            for (int c = 0; c < C; c++) col[c] = background[c];
+            return false;
+        }
+        int g, v[3];
+        bool rev;
+        winner_verts(fn, F, S, faces, true, g, rev, v);
+        float w[3], z[3], a[3];
+        for (int k = 0; k < 3; k++) {
+            w[k] = bary[3 * si + k];
+            z[k] = verts[((size_t)b * N + v[k]) * 3 + 2];
+        }
+        const float depth = persp_weights(w, z, a);
+        cube_coord(w, z, depth, ts, eps).read(tex + ((size_t)b * F + g) * ts * ts * ts * C, rev, ts, C, col);
+        return true;
+    };
+    for (long i = 0; i < (long)B * S * S; i++) resolve_pixel(i, S, ssaa, C, rgb, alpha, sample);
+    return 0;
+}
+
+// backward: same per-sample arithmetic as raster_bwd_samples + scatter_project (serial adds).
 extern "C" int g2s_emul_render_depth_bwd(const float *verts, const int *faces, const float *grad_depth,
                                          const int *face_idx, const float *bary, int B, int N, int F,
                                          int S, const float *K, float orig_size, int ssaa,
@@ -154,11 +193,9 @@ extern "C" int g2s_emul_render_depth_bwd(const float *verts, const int *faces, c
         const int yi = pn / is, xi = pn % is, fr = is - 1 - yi;
         const float g = grad_depth[((size_t)b * S + fr / ssaa) * S + xi / ssaa] / (float)(ssaa * ssaa);
         if (g == 0.0f) continue;
-        int v[3];
-        const int gi = fn % F;
-        if (faces) { v[0] = faces[3 * gi]; v[1] = faces[3 * gi + 1]; v[2] = faces[3 * gi + 2]; }
-        else implicit_face(gi, S, v);
-        if (fn >= F) std::swap(v[0], v[2]);
+        int v[3], gi;
+        bool rev;
+        winner_verts(fn, F, S, faces, true, gi, rev, v);
         float px[3], py[3], pz[3];
         for (int k = 0; k < 3; k++) {
             const float *q = verts + ((size_t)b * N + v[k]) * 3;

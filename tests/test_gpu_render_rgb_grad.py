@@ -64,8 +64,11 @@ FIT_RATIO = 0.01
 # ------------------------------------------------------------------------------------- the restatement
 def restate(verts, faces, tex, face_idx, S, K, ssaa=2, background=(1.0, 1.0, 1.0), eps=EPS, orig_size=None):
     """float64 texture pass.  verts [B,N,3], tex [B,F,ts,ts,ts,C] float64 tensors (differentiable);
-    faces (F,3) and face_idx [B,is,is] integer arrays (data).  Returns [B,C,S,S]."""
+    faces (F,3) and face_idx [B,is,is] integer arrays (data).  Returns [B,C,S,S].  Every operation runs in the
+    dtype of `verts`, so float32 inputs give the float32 evaluation of the same formula (the yardstick of
+    tests/test_raster_core_cpu.py)."""
     B, N, _ = verts.shape
+    dt = verts.dtype
     F, ts, Cc = tex.shape[1], tex.shape[2], tex.shape[5]
     isz = S * ssaa
     osz = float(S if orig_size is None else orig_size)
@@ -90,7 +93,7 @@ def restate(verts, faces, tex, face_idx, S, K, ssaa=2, background=(1.0, 1.0, 1.0
     p0 = 0.5 * (pu * isz + isz - 1.0)
     p1 = 0.5 * (pv * isz + isz - 1.0)
     den = p0[:, 2] * (p1[:, 0] - p1[:, 1]) + p0[:, 0] * (p1[:, 1] - p1[:, 2]) + p0[:, 1] * (p1[:, 2] - p1[:, 0])
-    xf, yf = xi.double(), yi.double()
+    xf, yf = xi.to(dt), yi.to(dt)
     w = torch.stack([
         ((p1[:, 1] - p1[:, 2]) * xf + (p0[:, 2] - p0[:, 1]) * yf + (p0[:, 1] * p1[:, 2] - p0[:, 2] * p1[:, 1])) / den,
         ((p1[:, 2] - p1[:, 0]) * xf + (p0[:, 0] - p0[:, 2]) * yf + (p0[:, 2] * p1[:, 0] - p0[:, 0] * p1[:, 2])) / den,
@@ -102,8 +105,8 @@ def restate(verts, faces, tex, face_idx, S, K, ssaa=2, background=(1.0, 1.0, 1.0
     t = (w * float(ts - 1) * (depth / pz)).clamp(min=0.0)
     t = torch.minimum(t, torch.full_like(t, float(ts - 1) - eps))
     base = t.detach().to(torch.long)                                       # C cast: truncation
-    frac = t - base.double()
-    col = torch.zeros((fn.shape[0], Cc), dtype=torch.float64)
+    frac = t - base.to(dt)
+    col = torch.zeros((fn.shape[0], Cc), dtype=dt)
     for pn in range(8):
         wt = torch.ones_like(frac[:, 0])
         idx = []
@@ -117,7 +120,7 @@ def restate(verts, faces, tex, face_idx, S, K, ssaa=2, background=(1.0, 1.0, 1.0
         i0 = torch.where(rev, idx[2], idx[0])                              # reversed copy: axes 0 and 2 swapped
         i2 = torch.where(rev, idx[0], idx[2])
         col = col + wt[:, None] * tex[bn, g, i0, idx[1], i2]
-    ss = torch.as_tensor(np.asarray(background, np.float64)[:Cc]).expand(B, isz, isz, Cc).contiguous()
+    ss = torch.as_tensor(np.asarray(background, np.float64)[:Cc]).to(dt).expand(B, isz, isz, Cc).contiguous()
     ss = ss.index_put((bn, yi, xi), col)
     ss = ss.flip(1).permute(0, 3, 1, 2)                                    # vertical flip, [B, C, is, is]
     return ss.reshape(B, Cc, S, ssaa, S, ssaa).sum((3, 5)) * (1.0 / (ssaa * ssaa))

@@ -205,6 +205,29 @@ def test_renderer_utils_golden(golden):
         ru.get_textures_from_im(im, 3)
 
 
+def test_render_rgb_refuses_lens_distortion():
+    """Every render method takes its camera from Renderer._camera: non-zero dist_coeffs raise NotImplementedError
+    before any device call (CPU tensors reach nothing else), from the argument and from the constructor."""
+    from gan2shape_amd.plugins import neural_renderer as nr
+    S = 4
+    K = torch.tensor([[[2.0, 0, 2], [0, 2.0, 2], [0, 0, 1]]])
+    verts = torch.rand(1, S * S, 3) + 1.0
+    tex = torch.zeros(1, 2 * (S - 1) ** 2, 2, 2, 2, 3)
+    dist = torch.tensor([[0.1, 0.0, 0.0, 0.0, 0.0]])
+    r = nr.Renderer(camera_mode='projection', K=K, image_size=S, orig_size=S)
+    with pytest.raises(NotImplementedError, match="lens distortion"):
+        r.render_rgb(verts, None, tex, dist_coeffs=dist)
+    r = nr.Renderer(camera_mode='projection', K=K, image_size=S, orig_size=S, dist_coeffs=dist)
+    for call in (lambda: r.render_rgb(verts, None, tex), lambda: r.render(verts, None, tex),
+                 lambda: r.render_depth(verts, None), lambda: r.render_silhouettes(verts, None)):
+        with pytest.raises(NotImplementedError, match="lens distortion"):
+            call()
+    # zero coefficients are no distortion: the call goes on to the device check
+    r = nr.Renderer(camera_mode='projection', K=K, image_size=S, orig_size=S, dist_coeffs=torch.zeros(1, 5))
+    with pytest.raises(RuntimeError, match="CUDA"):
+        r.render_rgb(verts, None, tex)
+
+
 def test_renderer_geometry_golden(golden):
     g = golden("geometry")
     S = g["r.depth"].shape[1]

@@ -112,6 +112,85 @@ def test_backward_arithmetic(emul):
         np.testing.assert_allclose(gv, ref, atol=2e-5 * scale)
 
 
+# ----------------------------------------------------------------------------- the texture pass (shade_core.h)
+def test_winner_verts_on_a_grid_with_reversed_copies(emul):
+    """Every id of an S = 5 grid with fill_back, through the face list and through the implicit topology: the
+    triple is the grid's face, flipped for the reversed copy (ids >= F); without reversed copies nothing flips."""
+    import torch
+    from gan2shape_amd.plugins.neural_renderer import _regular_grid_faces
+    S = 5
+    faces = np.ascontiguousarray(_regular_grid_faces(S, torch.device("cpu")).numpy(), np.int32)
+    F = faces.shape[0]
+    assert F == 2 * (S - 1) ** 2
+    ids = np.arange(2 * F)
+    want = np.where((ids >= F)[:, None], faces[ids % F][:, ::-1], faces[ids % F])
+    for fptr in (faces, None):
+        for reversible in (1, 0):
+            g, rev, v = np.empty(2 * F, np.int32), np.empty(2 * F, np.int32), np.empty((2 * F, 3), np.int32)
+            emul.g2s_emul_winner_verts(2 * F, F, S, _i(fptr), reversible, _i(g), _i(rev), _i(v))
+            np.testing.assert_array_equal(g, ids % F)
+            np.testing.assert_array_equal(rev, (ids >= F) if reversible else np.zeros(2 * F))
+            np.testing.assert_array_equal(v, want if reversible else faces[ids % F])
+
+
+# keys of test_gpu_render_rgb_grad.CASES (S, ts, C, fill_back, implicit): both topologies, fill_back on and off,
+# C of 1 and 3; each runs with ssaa 2 and 1
+RGB_CASES = [(16, 2, 3, True, True), (20, 2, 3, True, False), (12, 2, 1, False, True)]
+
+
+@pytest.mark.parametrize("key", RGB_CASES, ids=str)
+def test_texture_forward_from_the_shared_header(emul, key):
+    """g2s_emul_render_rgb — winner_verts, persp_weights, CubeCoord and resolve_pixel as the kernels compile them —
+    on the maps the emulated depth pass produced, against the float64 restatement of test_gpu_render_rgb_grad on
+    the same winners.  Yardstick: the restatement evaluated in float32, another fp32 evaluation of the same
+    formula that may associate differently; the emulation's relative L2 error may be at most twice its error.
+
+    The scenes of these cases have no reversed winner, so each fill_back case runs a second time on the same maps
+    with every winner replaced by its reversed copy: the id plus F and the three weights in the opposite order, which
+    is what the depth pass stores for the triple (v2, v1, v0) at the same sample.
+
+    Measured, emulation / yardstick (ratio); the reversed maps give the same figures to three digits:
+        (16, 2, 3, True, True)    ssaa 2  2.86e-6 / 2.76e-6 (1.04)   ssaa 1  4.81e-6 / 4.77e-6 (1.01)
+        (20, 2, 3, True, False)   ssaa 2  1.73e-6 / 1.73e-6 (1.00)   ssaa 1  1.35e-5 / 9.96e-6 (1.36)
+        (12, 2, 1, False, True)   ssaa 2  8.49e-7 / 8.29e-7 (1.02)   ssaa 1  1.17e-6 / 1.12e-6 (1.04)"""
+    import torch
+    import test_gpu_render_rgb_grad as rg
+    assert key in rg.CASES
+    S, ts, Cc, fill_back, implicit = key
+    geo, verts, faces, tex, _ = rg.make_case(S, ts, Cc)
+    B, N, _ = verts.shape
+    F = faces.shape[0]
+    bg = np.array([1.0, 0.5, -0.25][:Cc], np.float32)
+    for ssaa in (2, 1):
+        maps = run_emul(emul, verts, faces, S, geo.K[0], ssaa, fill_back, near=rg.NEAR, far=rg.FAR, implicit=implicit)
+        assert (maps["face_idx"] >= 0).mean() > 0.1
+        for reverse in ((False, True) if fill_back else (False,)):
+            fidx, bary = maps["face_idx"], maps["bary"]
+            if reverse:
+                assert (fidx < F).all()
+                fidx = np.where(fidx >= 0, fidx + F, fidx).astype(np.int32)
+                bary = np.ascontiguousarray(bary[..., ::-1])
+            rgb = np.full((B, Cc, S, S), np.nan, np.float32)
+            alpha = np.full((B, S, S), np.nan, np.float32)
+            rc = emul.g2s_emul_render_rgb(_f(verts), _i(None if implicit else faces), _i(fidx), _f(bary), _f(tex),
+                                          B, N, F, S, ssaa, ts, Cc, _f(bg), C.c_float(rg.EPS), _f(rgb), _f(alpha))
+            assert rc == 0
+            ref = {dt: rg.restate(torch.tensor(verts, dtype=dt), faces, torch.tensor(tex, dtype=dt), fidx, S, geo.K[0],
+                                  ssaa=ssaa, background=bg.tolist(), eps=rg.EPS)
+                   for dt in (torch.float64, torch.float32)}
+            assert ref[torch.float32].dtype == torch.float32
+            want = ref[torch.float64].numpy()
+            err = float(np.linalg.norm(rgb.astype(np.float64) - want) / np.linalg.norm(want))
+            yard = float(np.linalg.norm(ref[torch.float32].numpy().astype(np.float64) - want) / np.linalg.norm(want))
+            print(f"texture forward {key} ssaa={ssaa} reversed={reverse}: emulation rel L2 {err:.3e}  float32 "
+                  f"restatement {yard:.3e}  ratio {err / yard:.2f}")
+            assert yard > 0
+            assert err <= 2 * yard, (key, ssaa, reverse, err, yard)
+            # alpha: the share of a pixel's samples with a winner, exactly
+            cov = (fidx >= 0)[:, ::-1].reshape(B, S, ssaa, S, ssaa).sum((2, 4)) / float(ssaa * ssaa)
+            np.testing.assert_array_equal(alpha, cov.astype(np.float32))
+
+
 # ----------------------------------------------------------------------------- the depth-path case table
 def test_case_table_reaches_its_paths():
     """What keeps the GPU tests of tests/test_gpu_raster_paths.py from passing with a path unvisited,
