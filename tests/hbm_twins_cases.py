@@ -42,6 +42,7 @@ WL1_COMBOS = [(xo, na) for xo in (1, 0) for na in (0, 1, 2) if xo or na]     # a
 DEMOD = [(2, 5, 3), (3, 70, 9)]
 DEMOD_MULTI_B = 3
 EPS = 1e-8
+TAIL_NW, BLUR_NW, ROWS_NW = -0.37, -0.8, 0.6      # the noise weights (device scalars)
 
 
 def _rng(*key):
@@ -70,13 +71,19 @@ def taps(t):
     return k / 16
 
 
+def tail_inputs(B, C, HW):
+    """x [B, C, HW], noise [B, HW], bias [C], noise weight (numpy, float32)."""
+    rng = _rng(1, B, C, HW)
+    x, noise, bias = _f32(rng, B, C, HW), _f32(rng, B, HW), _f32(rng, C)
+    x[:, :, 1] = -bias[None, :]          # pre-activations that are exactly 0 where the map is 0
+    noise[:, 1] = 0.0
+    return x, noise, bias, TAIL_NW
+
+
 def run_tail(L, lib, res):
     for name, B, C, HW, variant in TAIL:
-        rng = _rng(1, B, C, HW)
-        x, noise, bias = _f32(rng, B, C, HW), _f32(rng, B, HW), _f32(rng, C)
-        x[:, :, 1] = -bias[None, :]          # pre-activations that are exactly 0 where the map is 0
-        noise[:, 1] = 0.0
-        nd, bd, nwd = dev(noise), dev(bias), dev([-0.37])
+        x, noise, bias, nw = tail_inputs(B, C, HW)
+        nd, bd, nwd = dev(noise), dev(bias), dev([nw])
         for entry, nz in (("shared", nd[0].contiguous()), ("ps", nd)):
             if variant == "nonoise":
                 if entry == "ps":
@@ -92,15 +99,27 @@ def run_tail(L, lib, res):
             res[f"tail.{name}.{entry}"] = y
 
 
+def blur_inputs(ih, iw, t):
+    """x [B, C, ih, iw], taps [kh, kh], noise [B, oh, ow], bias [C], noise weight (numpy, float32)."""
+    B, C = BLUR_B, BLUR_C
+    rng = _rng(2, ih, iw)
+    k = taps(t)
+    kh = k.shape[0]
+    oh, ow = ih + 2 - kh + 1, iw + 2 - kh + 1
+    return _f32(rng, B, C, ih, iw), k, _f32(rng, B, oh, ow), _f32(rng, C), BLUR_NW
+
+
+def plain_blur_inputs():
+    """x [B, C, 10, 10] and the taps of the plain up = 2 entry."""
+    return _f32(_rng(2, 0), BLUR_B, BLUR_C, 10, 10), taps((1, 3, 3, 1))
+
+
 def run_blur(L, lib, res):
     B, C = BLUR_B, BLUR_C
     for name, ih, iw, t in BLUR:
-        rng = _rng(2, ih, iw)
-        k = taps(t)
-        kh = k.shape[0]
-        oh, ow = ih + 2 - kh + 1, iw + 2 - kh + 1
-        x, noise, bias = _f32(rng, B, C, ih, iw), _f32(rng, B, oh, ow), _f32(rng, C)
-        xd, kd, nd, bd, nwd = dev(x), dev(k), dev(noise), dev(bias), dev([-0.8])
+        x, k, noise, bias, nw = blur_inputs(ih, iw, t)
+        kh, (oh, ow) = k.shape[0], noise.shape[1:]
+        xd, kd, nd, bd, nwd = dev(x), dev(k), dev(noise), dev(bias), dev([nw])
         for entry, nz in (("shared", nd[0].contiguous()), ("ps", nd)):
             y = torch.full((B, C, oh, ow), float("nan"), device="cuda")
             fn = L.g2s_upfirdn2d_nba if entry == "shared" else L.g2s_upfirdn2d_nba_ps
@@ -108,8 +127,8 @@ def run_blur(L, lib, res):
                          lib.ptr(nz), lib.ptr(nwd), ALPHA, GAIN, lib.stream()))
             res[f"blur.{name}.{entry}"] = y
     # the plain entry shares the store: no tail, up = 2 (the polyphase path), float32 and float16
-    rng = _rng(2, 0)
-    x, kd = _f32(rng, B, C, 10, 10), dev(taps((1, 3, 3, 1)))
+    x, k = plain_blur_inputs()
+    kd = dev(k)
     for dname, dtype, code in (("f32", torch.float32, 0), ("f16", torch.float16, 1)):
         xd = dev(x).to(dtype)
         y = torch.full((B, C, 19, 19), float("nan"), device="cuda", dtype=dtype)
@@ -118,14 +137,21 @@ def run_blur(L, lib, res):
         res[f"blur.plain_up2.{dname}"] = y
 
 
+def rows_inputs(B, C, H):
+    """x, g1, g2 [B, C, n], s1, s2, demod [B, C], noise [B, n], bias [C], noise weight (numpy, float32)."""
+    n = H * H
+    rng = _rng(3, B, C, H)
+    x, g1, g2 = _f32(rng, B, C, n), _f32(rng, B, C, n), _f32(rng, B, C, n)
+    s1, s2, demod = _f32(rng, B, C), _f32(rng, B, C), (0.5 + rng.random((B, C))).astype(np.float32)
+    noise, bias = _f32(rng, B, n), _f32(rng, C)
+    return x, g1, g2, s1, s2, demod, noise, bias, ROWS_NW
+
+
 def run_rows(L, lib, res):
     for B, C, H in ROWS:
         n = H * H
-        rng = _rng(3, B, C, H)
-        x, g1, g2 = _f32(rng, B, C, n), _f32(rng, B, C, n), _f32(rng, B, C, n)
-        s1, s2, demod = _f32(rng, B, C), _f32(rng, B, C), (0.5 + rng.random((B, C))).astype(np.float32)
-        noise, bias = _f32(rng, B, n), _f32(rng, C)
-        xd, g1d, g2d, s1d, s2d, dmd, nd, bd, nwd = (dev(a) for a in (x, g1, g2, s1, s2, demod, noise, bias, [0.6]))
+        x, g1, g2, s1, s2, demod, noise, bias, nw = rows_inputs(B, C, H)
+        xd, g1d, g2d, s1d, s2d, dmd, nd, bd, nwd = (dev(a) for a in (x, g1, g2, s1, s2, demod, noise, bias, [nw]))
         for entry, nz in (("shared", nd[0].contiguous()), ("ps", nd)):
             fn = L.g2s_synth_bwd_rows if entry == "shared" else L.g2s_synth_bwd_rows_ps
             for two in (False, True):
@@ -144,14 +170,23 @@ def run_rows(L, lib, res):
                         res[key + ".gdot"] = gdot
 
 
-def run_wl1(L, lib, res):
+WL1_G, WL1_DEN, WL1_COEF, WL1_ADD_SCALE = 0.7, 3.0, 0.3, 2 ** -0.5
+
+
+def wl1_inputs():
+    """x, y, gadd, gadd2, gate reference [B, C, HW] and w [B, HW] (numpy, float32)."""
     B, C, HW = WL1
     rng = _rng(4)
     x, y, gadd, gadd2, ref = (_f32(rng, B, C, HW) for _ in range(5))
     y[:, :, 2] = x[:, :, 2]                      # ties: sign(0) = 0
     w = rng.random((B, HW)).astype(np.float32)
-    xd, yd, wd, ad, a2d, rd = (dev(a) for a in (x, y, w, gadd, gadd2, ref))
-    g, den, coef = dev([0.7]), dev([3.0]), dev([0.3])
+    return x, y, w, gadd, gadd2, ref
+
+
+def run_wl1(L, lib, res):
+    B, C, HW = WL1
+    xd, yd, wd, ad, a2d, rd = (dev(a) for a in wl1_inputs())
+    g, den, coef = dev([WL1_G]), dev([WL1_DEN]), dev([WL1_COEF])
     sz = (B, C, HW)
     new = lambda: torch.full(sz, float("nan"), device="cuda")      # noqa: E731
     p, st = lib.ptr, lib.stream
@@ -169,7 +204,7 @@ def run_wl1(L, lib, res):
                 gq = new() if outs != "gx" else None
                 lib.check(L.g2s_weighted_l1_bwd3(
                     p(xd if xo else None), p(yd if xo else None), p(wv if xo else None), p(g if xo else None),
-                    p(den if xo else None), p(ad if na else None), p(a2d if na == 2 else None), 2 ** -0.5, p(gx),
+                    p(den if xo else None), p(ad if na else None), p(a2d if na == 2 else None), WL1_ADD_SCALE, p(gx),
                     p(rd if gq is not None else None), ALPHA, GAIN, p(gq), *sz, st()))
                 if gx is not None:
                     res[f"wl1.{wname}.bwd3.x{xo}a{na}.{outs}.gx"] = gx
@@ -177,10 +212,15 @@ def run_wl1(L, lib, res):
                     res[f"wl1.{wname}.bwd3.x{xo}a{na}.{outs}.gate"] = gq
 
 
-def _demod_inputs(B, Cin, Cout):
+def demod_inputs(B, Cin, Cout):
+    """wsq [Cout, Cin], s [B, Cin], gd [B, Cout], gs_add [B, Cin] (numpy, float32)."""
     rng = _rng(5, B, Cin, Cout)
     wsq = (rng.random((Cout, Cin)) + 0.1).astype(np.float32)
-    return [dev(a) for a in (wsq, _f32(rng, B, Cin), _f32(rng, B, Cout), _f32(rng, B, Cin))]     # wsq, s, gd, gs_add
+    return wsq, _f32(rng, B, Cin), _f32(rng, B, Cout), _f32(rng, B, Cin)
+
+
+def _demod_inputs(B, Cin, Cout):
+    return [dev(a) for a in demod_inputs(B, Cin, Cout)]
 
 
 def run_demod(L, lib, res):

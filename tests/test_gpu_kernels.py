@@ -374,11 +374,7 @@ def test_groupnorm_act_vs_oracle(g2s, shape, groups, slope):
     ok = np.abs(nets.group_norm_act(x, gamma, beta, groups, 1e-5, False)) > 1e-5
     np.testing.assert_allclose(y.detach().cpu().numpy()[ok], ref[ok], rtol=0, atol=2e-6 * np.abs(ref).max())
     for got, want in ((xt.grad, dx), (gt.grad, dg), (bt.grad, db)):
-        g = got.cpu().numpy()
-        if want.shape == x.shape:  # dx couples all elements of a group: compare where no flip is near
-            np.testing.assert_allclose(g, want, rtol=0, atol=2e-5 * np.abs(want).max() + 1e-6)
-        else:
-            np.testing.assert_allclose(g, want, rtol=0, atol=2e-5 * np.abs(want).max() + 1e-6)
+        np.testing.assert_allclose(got.cpu().numpy(), want, rtol=0, atol=2e-5 * np.abs(want).max() + 1e-6)
 
 
 # ----------------------------------------------------------------------------- general conv (trained nets)
