@@ -47,6 +47,7 @@ SOURCES = {
     "conv_wgrad.hip": [],
     "adam.hip": [],
     "ada.hip": [],
+    "dtrain.hip": [],
     "probe.hip": [],
 }
 # The kernels take their descriptor struct by value.  Clang copies such a parameter into a private

@@ -25,6 +25,7 @@ from torch.nn import functional as F
 from . import synthesis
 from .modconv import DOWN2, PLAIN, UP2, conv2d, conv2d_supported, conv_bias_act, modconv, modconv_demod
 from .op import FusedLeakyReLU, add_bias_scale, clamp, fused_leaky_relu, fused_noise_bias_act, upfirdn2d
+from .op import conv2d_gradfix, mbstd
 
 
 class PixelNorm(nn.Module):
@@ -120,6 +121,9 @@ class EqualConv2d(nn.Module):
     def forward(self, input):
         w = self._w.get(self.weight, self.scale)
         mode = conv2d_supported(input, w, self.stride, self.padding)
+        if conv2d_gradfix.ENABLED and mode is not None:   # D under training: trainable, twice differentiable
+            out = conv2d_gradfix.conv2d(input, w, mode)
+            return out if self.bias is None else out + self.bias.view(1, -1, 1, 1)
         if mode is not None and (input.shape[0] * input.shape[2] * input.shape[3] >= 1024):
             out = conv2d(input, w, mode)       # fp32-MFMA implicit GEMM (g2s_modconv, no scales)
             return out if self.bias is None else out + self.bias.view(1, -1, 1, 1)
@@ -550,6 +554,16 @@ class ConvLayer(nn.Sequential):
 
     def forward(self, input):
         conv, act = self[-2], self[-1]
+        # D under training (conv2d_gradfix.use()): the same single launch with gradients to weight and bias and a
+        # second backward; below the size rule the Sequential's conv, then fused_leaky_relu
+        if (conv2d_gradfix.ENABLED and isinstance(act, FusedLeakyReLU) and isinstance(conv, EqualConv2d)
+                and conv.bias is None and input.is_cuda):
+            x = self[0](input) if len(self) == 3 else input
+            w = conv._w.get(conv.weight, conv.scale)
+            mode = conv2d_supported(x, w, conv.stride, conv.padding)
+            if mode is not None and x.shape[0] * x.shape[2] * x.shape[3] >= 1024:
+                return conv2d_gradfix.conv_bias_act(x, w, act.bias, mode, act.negative_slope, act.scale)
+            return act(conv(x))
         # frozen D on the GPU: convolution + bias + leaky-ReLU * sqrt(2) in one launch of the MFMA
         # kernel instead of conv, then an elementwise pass over the activation
         if (isinstance(act, FusedLeakyReLU) and isinstance(conv, EqualConv2d) and conv.bias is None
@@ -619,7 +633,10 @@ class Discriminator(nn.Module):
                 features.append(out)
             if len(features) >= ftr_num:
                 return 0, features
-        out = torch.cat([out, self._group_stddev(out)], 1)
+        if conv2d_gradfix.ENABLED and mbstd.supported(out, self.stddev_group, self.stddev_feat):
+            out = mbstd.minibatch_stddev(out, self.stddev_feat)     # copy + maps, backward and double backward: one launch each
+        else:
+            out = torch.cat([out, self._group_stddev(out)], 1)
         out = self.final_conv(out)
         features.append(out)
         out = self.final_linear(out.flatten(1))

@@ -972,6 +972,38 @@ int g2s_ada_warp_down(const float *x2, const float *Ginv, const float *Cmat, flo
 int g2s_ada_warp_down_bwd(const float *gy, const float *Ginv, const float *Cmat, float *gx2, int B, int C, int H,
                           int W, int H2, int W2, int acc_is_zero, g2s_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------
+ * Discriminator training (csrc/dtrain.hip): minibatch stddev, logistic loss, R1 penalty.  f32, fixed summation
+ * order, no atomics: bit-identical from run to run in either mode of g2s_set_deterministic.  Every check precedes
+ * the first launch; nothing allocates or synchronises.
+ *
+ * Minibatch stddev (stylegan2-pytorch/model.py:756-765).  x [B, C, H, W]; G = min(B, 4) members per group (B a
+ * multiple of G), member g of group n is sample g * (B / G) + n; F feature blocks of C / F channels.
+ *   d = x - mean_g x,  s = sqrt(mean_g d^2 + 1e-8),  f[n, j] = mean of s over block j's E = (C / F) H W elements.
+ * g2s_mbstd_fwd: out [B, C + F, H, W] = x followed by the F constant maps f[n(b), j] — one launch, no cat.
+ * g2s_mbstd_bwd: gout [B, C + F, H, W], x -> gx [B, C, H, W] = gout[:, :C] + a d / s with
+ *   a[n, j] = (sum_{g,h,w} gout[b, C + j, h, w]) / (E G).
+ * g2s_mbstd_bwd2: the backward of g2s_mbstd_bwd for a cotangent ggx [B, C, H, W] on gx:
+ *   ggout [B, C + F, H, W]: ggx, then on each appended map sum_{g,e} ggx_g d_g / (s E G);
+ *   xg [B, C, H, W] = a [ (ggx_h - mean_g ggx) / s - d_h (sum_g ggx_g d_g) / (G s^3) ], the gradient on x.
+ *
+ * g2s_d_logistic (train.py:64-68): real [Br], fake [Bf] -> out[4] = { mean softplus(-real) + mean softplus(fake),
+ *   mean real, mean fake, sum sign(real) }; g_real [Br] = -sigmoid(-real) / Br and g_fake [Bf] = sigmoid(fake) / Bf,
+ *   the gradients of out[0], where the pointers are not NULL.  softplus(x) = max(x, 0) + log1p(exp(-|x|)).
+ * g2s_r1_penalty (train.py:71-78): grad [B, n] -> per_sample [B] = sum_i grad[b, i]^2 and, where mean is not NULL,
+ *   mean[0] = their mean.  Two stages: partial [B * g2s_r1_penalty_chunks(n)] floats of scratch hold the sums of
+ *   fixed chunks, a second launch adds them in index order.  B <= 65535.
+ * ---------------------------------------------------------------------------------------- */
+int g2s_mbstd_fwd(const float *x, float *out, int B, int C, int H, int W, int F, g2s_stream_t stream);
+int g2s_mbstd_bwd(const float *gout, const float *x, float *gx, int B, int C, int H, int W, int F, g2s_stream_t stream);
+int g2s_mbstd_bwd2(const float *ggx, const float *gout, const float *x, float *ggout, float *xg, int B, int C, int H,
+                   int W, int F, g2s_stream_t stream);
+int g2s_d_logistic(const float *real, const float *fake, float *out, float *g_real, float *g_fake, int Br, int Bf,
+                   g2s_stream_t stream);
+int64_t g2s_r1_penalty_chunks(int64_t n);
+int g2s_r1_penalty(const float *grad, float *per_sample, float *mean, float *partial, int B, int64_t n,
+                   g2s_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
