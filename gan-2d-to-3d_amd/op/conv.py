@@ -201,6 +201,8 @@ def supported(mod, x):
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
         return False
     k = mod.kernel_size
+    if k[0] == 5 and mod.stride[0] == 2:   # scatter classes of 9 / 6 / 6 / 4 taps: the kernel has no 6-tap body
+        return False
     return (k[0] == k[1] and 1 <= k[0] <= 5 and mod.stride[0] == mod.stride[1] and mod.stride[0] in (1, 2)
             and mod.padding[0] == mod.padding[1] and isinstance(mod.padding[0], int) and 0 <= mod.padding[0] < k[0]
             and mod.dilation == (1, 1) and mod.groups == 1 and mod.padding_mode == 'zeros'
