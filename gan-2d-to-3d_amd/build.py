@@ -48,6 +48,7 @@ SOURCES = {
     "adam.hip": [],
     "ada.hip": [],
     "dtrain.hip": [],
+    "gtrain.hip": [],
     "probe.hip": [],
 }
 # The kernels take their descriptor struct by value.  Clang copies such a parameter into a private

@@ -26,9 +26,14 @@ struct WgradParams {
 };
 
 // One workgroup of the weight-gradient GEMM: (bx, by, bz) = (output tile, pixel slice, group).
+// SCALED (csrc/gtrain.hip, the modulated weight gradient): A[b, a, .] is multiplied by sa[b, a] and G[b, g, .] by
+// sg[b, g] as they are loaded (either pointer may be NULL).  The sample b is that of the loaded element, not of the
+// K tile: a 4 x 4 map puts two samples into one 32-pixel tile.  SCALED = false compiles to the unscaled code.
+template <bool SCALED = false>
 __device__ __forceinline__ void wgrad_block(const WgradParams &p, float (&As)[WG_BK][WG_BM + 1],
                                             float (&Bs)[WG_BK][WG_BN + 1], const int bx, const int by,
-                                            const int bz) {
+                                            const int bz, const float *__restrict__ sa = nullptr,
+                                            const float *__restrict__ sg = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, lk = lane >> 5;
     const int tiles_m = (p.Ca + WG_BM - 1) / WG_BM;
@@ -40,7 +45,7 @@ __device__ __forceinline__ void wgrad_block(const WgradParams &p, float (&As)[WG
 
     // this thread's elements: pixel lane kl fixed, rows (a or n) r0 + 8 e
     const int kl = tid & 31, r0 = tid >> 5;
-    int gbase[WG_E], dy[WG_E], dx[WG_E];
+    int gbase[WG_E], dy[WG_E], dx[WG_E], gch[WG_E];
     bool nok[WG_E], aok[WG_E];
 #pragma unroll
     for (int e = 0; e < WG_E; e++) {
@@ -48,6 +53,7 @@ __device__ __forceinline__ void wgrad_block(const WgradParams &p, float (&As)[WG
         nok[e] = n < p.N;
         const int g = n / KK, t = n - g * KK;
         gbase[e] = g * p.GH * p.GW;
+        gch[e] = g;
         dy[e] = t / p.k - p.pad;
         dx[e] = t % p.k - p.pad;
         aok[e] = m0 + r0 + 8 * e < p.Ca;
@@ -67,6 +73,10 @@ __device__ __forceinline__ void wgrad_block(const WgradParams &p, float (&As)[WG
             const int gy = gy0 + dy[e], gx = gx0 + dx[e];
             const bool ok = kok && nok[e] && gy >= 0 && gy < p.GH && gx >= 0 && gx < p.GW;
             rb[e] = ok ? gp[gbase[e] + gy * p.GW + gx] : 0.0f;
+            if constexpr (SCALED) {
+                if (sa && kok && aok[e]) ra[e] *= sa[(size_t)b * Ca_tot + grp * p.Ca + m0 + r0 + 8 * e];
+                if (sg && ok) rb[e] *= sg[(size_t)b * Cg_tot + grp * p.Cg + gch[e]];
+            }
         }
     };
     wg_f32x16 acc;

@@ -1,6 +1,6 @@
 """The discriminator half of stylegan2-pytorch/train.py: logistic loss every step, lazy R1 every `d_reg_every`-th,
 ADA on both — enough to adapt the discriminator whose features drive GAN2Shape's step-3 loss to a few thousand images
-of one's own.  The generator half (modulated weight gradients, path-length regularisation, g_ema) is not built.
+of one's own.  The generator half (modulated weight gradients, path-length regularisation, g_ema) is gtrain.py.
 
     python -m gan2shape_amd.dtrain --ckpt G_D.pt --size 128 --channel-multiplier 1 --data root/car --iter 2000 \
         --batch 16 [--augment] [--augment-p 0] [--r1 10] [--d-reg-every 16] [--seed 0] --out ckpts/d_ft.pt

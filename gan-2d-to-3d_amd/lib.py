@@ -139,6 +139,11 @@ SIGNATURES = {
     "g2s_d_logistic": (_i, [_p, _p, _p, _p, _p, _i, _i, _p]),
     "g2s_r1_penalty_chunks": (_i64, [_i64]),
     "g2s_r1_penalty": (_i, [_p, _p, _p, _p, _i, _i64, _p]),
+    "g2s_modconv_wgrad": (_i, [_p, _p, _p, _p, _p] + [_i] * 10 + [_i, _p]),
+    "g2s_path_penalty": (_i, [_p, _p, _f, _p, _p, _p, _i, _i, _i, _p]),
+    "g2s_g_nonsaturating": (_i, [_p, _p, _p, _i, _p]),
+    "g2s_ema_chunk": (_i64, []),
+    "g2s_ema_accumulate": (_i, [_p, _p, _i, _i, _f, _f, _p]),
 }
 
 

@@ -227,7 +227,12 @@ class ModulatedConv2d(nn.Module):
     def forward(self, input, style):
         s = style.s if isinstance(style, PreStyle) else self.modulation(style)  # [B, Cin] (model.py:253)
         w, wsq = self._weights()
-        if self.demodulate:                             # model.py:256-258, one node with the convolution
+        if conv2d_gradfix.ENABLED and input.is_cuda and input.dtype == torch.float32:
+            # G under training: a node whose gradients differentiate again (path length step); the demodulation is
+            # the torch composition on [B, C] tensors
+            demod = torch.rsqrt(F.linear(s * s, wsq) + self.eps) if self.demodulate else None
+            conv = lambda x, mode: conv2d_gradfix.modulated_conv2d(x, w, s, demod, mode)   # noqa: E731
+        elif self.demodulate:                           # model.py:256-258, one node with the convolution
             conv = lambda x, mode: modconv_demod(x, w, s, wsq, self.eps, mode)   # noqa: E731
         else:
             conv = lambda x, mode: modconv(x, w, s, None, mode)                  # noqa: E731
@@ -281,6 +286,7 @@ class StyledConv(nn.Module):
         # the fused tail has no gradient for the map and no CPU form: a map that is being optimised (the projector's)
         # and CPU tensors take the two modules below
         fused = out.is_cuda and not (noise is not None and noise.requires_grad and torch.is_grad_enabled())
+        fused = fused and not conv2d_gradfix.ENABLED    # no gradient to the noise weight and the bias, none twice
         if fused and noise is not None and noise.shape[0] == 1 and (frozen or not torch.is_grad_enabled()):
             return fused_noise_bias_act(out, noise, self.noise.weight, self.activate.bias,
                                         self.activate.negative_slope, self.activate.scale)
@@ -501,7 +507,8 @@ class Generator(nn.Module):
             # one unbind instead of 2 * n_latent selects: the backward is a single stack, not a
             # zero-fill + copy + add per use (model.py:493-503 indexes latent[:, i] per layer)
             lat = self._batched_styles(latent.unbind(1))
-        if (self.ONE_NODE and not return_features and getattr(lat, 'pre', None) is not None
+        if (self.ONE_NODE and not conv2d_gradfix.ENABLED and not return_features
+                and getattr(lat, 'pre', None) is not None
                 and synthesis.eligible(self, out, [p.s for p in lat.pre], noise)):
             # the whole layer loop below as one autograd node with fused epilogues (synthesis.py)
             image = synthesis.synthesize(self, noise, out, [p.s for p in lat.pre])

@@ -1004,6 +1004,41 @@ int64_t g2s_r1_penalty_chunks(int64_t n);
 int g2s_r1_penalty(const float *grad, float *per_sample, float *mean, float *partial, int B, int64_t n,
                    g2s_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Generator training (csrc/gtrain.hip; gan2shape_amd/gtrain.py, op/conv2d_gradfix.py).  float32.
+ *
+ * g2s_modconv_wgrad: the weight gradient of the modulated convolution y = demod * conv(s * x, w),
+ *   dw[a,g,ky,kx] = sum_{b,py,px} sa[b,a] A[b,a,py,px] * sg[b,g] G[b,g,py*s+ky-p,px*s+kx-p]      (zero outside G)
+ *   A [B,Ca,PH,PW], G [B,Cg,GH,GW], sa [B,Ca] or NULL, sg [B,Cg] or NULL, dw [Ca,Cg,k,k] fully overwritten.  The
+ *   scales multiply the operands as they are loaded: neither product is written to memory.  Geometry, the split of
+ *   the pixel sum and dw_is_zero as g2s_conv2d_wgrad (groups = 1); with both scales NULL and
+ *   g2s_set_deterministic(1) the result is that of g2s_conv2d_wgrad bit for bit.
+ *
+ * g2s_path_penalty (train.py:94-100): grad [B, L, D], mean_path a DEVICE scalar (the running mean) ->
+ *   lengths [B] = sqrt(mean_l sum_d grad^2);  pm = mean_path + decay * (mean lengths - mean_path);
+ *   stats [3] = { mean_b (lengths - pm)^2, pm, mean lengths };  dgrad [B, L, D] (or NULL) = d stats[0] / d grad, with
+ *   pm a function of grad as in the reference.  One workgroup, fixed summation order.  B <= 1024.
+ * g2s_g_nonsaturating (train.py:81-84): fake [B] -> out[0] = mean softplus(-fake); g_fake [B] (or NULL) =
+ *   -sigmoid(-fake) / B.  One workgroup.
+ * g2s_ema_accumulate (train.py:50-55): dst = dst * decay + src * one_minus_decay for every tensor of a DEVICE table
+ *   in one launch.  chunk0 DEVICE [n_tensors + 1]: prefix sums of ceil(n / g2s_ema_chunk()); n_chunks =
+ *   chunk0[n_tensors].  16-byte accesses where both pointers of a tensor are 16-byte aligned.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct g2s_ema_tensor {
+    float *dst;
+    const float *src;
+    int64_t n;
+} g2s_ema_tensor;
+int g2s_modconv_wgrad(const float *A, const float *sa, const float *G, const float *sg, float *dw, int B, int Ca,
+                      int Cg, int PH, int PW, int GH, int GW, int k, int stride, int pad, int dw_is_zero,
+                      g2s_stream_t stream);
+int g2s_path_penalty(const float *grad, const float *mean_path, float decay, float *lengths, float *stats,
+                     float *dgrad, int B, int L, int D, g2s_stream_t stream);
+int g2s_g_nonsaturating(const float *fake, float *out, float *g_fake, int B, g2s_stream_t stream);
+int64_t g2s_ema_chunk(void);
+int g2s_ema_accumulate(const g2s_ema_tensor *tensors, const int *chunk0, int n_tensors, int n_chunks, float decay,
+                       float one_minus_decay, g2s_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
