@@ -49,6 +49,7 @@ SOURCES = {
     "ada.hip": [],
     "dtrain.hip": [],
     "gtrain.hip": [],
+    "dataprep.hip": [],
     "probe.hip": [],
 }
 # The kernels take their descriptor struct by value.  Clang copies such a parameter into a private

@@ -302,13 +302,24 @@ def real_batches(root, size, batch, generator):
             yield torch.stack(images)
 
 
+def batches(root, size, batch, generator, device):
+    """The real batches of a run: a folder packed by prepare_data.py (it holds `<size>.npy`) is served from device memory
+    by dataset.DeviceBatches; any other folder goes through real_batches.  Same draws from `generator` either way.
+    The batches may be on `device` already; `.to(device)` is then free."""
+    from .dataset import DeviceBatches, is_packed
+    if is_packed(root, size):
+        return DeviceBatches(root, size, batch, generator, device)
+    return real_batches(root, size, batch, generator)
+
+
 def build_parser():
     parser = argparse.ArgumentParser(prog="python -m gan2shape_amd.dtrain",
                                      description="Fine-tune a StyleGAN2 discriminator: logistic loss, lazy R1, ADA")
     parser.add_argument("--ckpt", required=True, help="checkpoint with 'g_ema' and 'd' ('g' is copied through)")
     parser.add_argument("--size", type=int, required=True)
     parser.add_argument("--channel-multiplier", dest="channel_multiplier", type=int, default=2)
-    parser.add_argument("--data", required=True, help="dataset folder with list.txt")
+    parser.add_argument("--data", required=True,
+                        help="dataset folder with list.txt, or one packed by prepare_data (it holds <size>.npy)")
     parser.add_argument("--iter", type=int, default=2000)
     parser.add_argument("--batch", type=int, default=16)
     parser.add_argument("--lr", type=float, default=0.002)
@@ -341,7 +352,7 @@ def main(argv=None):
                                    args.augment_p, args.ada_target, args.ada_length)
     host_rng = torch.Generator().manual_seed(args.seed)
     dev_rng = torch.Generator(device=device).manual_seed(args.seed)
-    reals = real_batches(args.data, args.size, args.batch, host_rng)
+    reals = batches(args.data, args.size, args.batch, host_rng, device)
     for i in range(args.iter):
         real = next(reals).to(device)
         fake, _ = generate.sample(g_ema, args.batch, generator=dev_rng, batched=True)

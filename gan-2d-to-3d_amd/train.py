@@ -27,7 +27,8 @@ def build_parser():
     parser.add_argument("--channel-multiplier", dest="channel_multiplier", type=int, default=2)
     parser.add_argument("--latent", type=int, default=512)
     parser.add_argument("--n-mlp", dest="n_mlp", type=int, default=8)
-    parser.add_argument("--data", required=True, help="dataset folder with list.txt")
+    parser.add_argument("--data", required=True,
+                        help="dataset folder with list.txt, or one packed by prepare_data (it holds <size>.npy)")
     parser.add_argument("--iter", type=int, default=800000)
     parser.add_argument("--batch", type=int, default=16)
     parser.add_argument("--lr", type=float, default=0.002)
@@ -101,7 +102,7 @@ def main(argv=None):
     device = torch.device(args.device)
     torch.manual_seed(args.seed)
     dt, gt = build_trainers(args, device)
-    reals = dtrain.real_batches(args.data, args.size, args.batch, torch.Generator().manual_seed(args.seed))
+    reals = dtrain.batches(args.data, args.size, args.batch, torch.Generator().manual_seed(args.seed), device)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     for i in range(args.iter):
         loss = iteration(dt, gt, next(reals).to(device), i)

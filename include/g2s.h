@@ -1039,6 +1039,31 @@ int64_t g2s_ema_chunk(void);
 int g2s_ema_accumulate(const g2s_ema_tensor *tensors, const int *chunk0, int n_tensors, int n_chunks, float decay,
                        float one_minus_decay, g2s_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Data path of the trainer (csrc/dataprep.hip; prepare_data.py, dataset.DeviceBatches).
+ *
+ * g2s_u8_batch: out[b, c, y, x] = t[data[idx[b], c, y, flip[b] ? S - 1 - x : x]], t[v] = float(v) / 255 rounded to
+ *   f32, then * 2 - 1 (dataset.ImageDataset's arithmetic, bit for bit).  data u8 [N, 3, S, S] planar; idx DEVICE
+ *   int64 [B] (what torch.randperm yields); flip DEVICE u8 [B]; out f32 [B, 3, S, S].  One launch, no host read-back.
+ *   16-byte loads and stores when S % 16 == 0 and data, out are 16-byte aligned, a scalar path otherwise.  An index
+ *   outside [0, N) reads nothing and fills its sample with NaN.
+ *
+ * g2s_resize_u8: Pillow's ImagingResample for 8-bit images with a crop window.  src u8 [N, H, W, 3] interleaved;
+ *   dst u8 [N, 3, oh_c, ow_c] planar = the window (left, top, ow_c, oh_c) of the image resized to [oh, ow].
+ *   kx int32 [ow, ksx], bx int32 [ow, 2] (first tap, tap count) and ky [oh, ksy], by [oh, 2]: DEVICE tables of 22-bit
+ *   fixed-point coefficients (prepare_data.resample_coeffs).  The horizontal pass runs first and is skipped when
+ *   ow == W (kx, bx may be NULL), the vertical pass second, skipped when oh == H (ky, by may be NULL); each
+ *   accumulates in int32 from 1 << 21, shifts right by 22 and clips to 0..255; the intermediate is u8.
+ *   tmp u8 [N, 3, rows, ow_c]: the intermediate, needed when both passes run; it holds the source rows
+ *   row0 .. row0 + rows, which must cover every vertical window of the crop (ignored when oh == H).
+ *   Windows are clamped to the source, so no table makes the kernels read outside their buffers.
+ * ---------------------------------------------------------------------------------------- */
+int g2s_u8_batch(const uint8_t *data, int64_t N, const int64_t *idx, const uint8_t *flip, float *out, int B, int S,
+                 g2s_stream_t stream);
+int g2s_resize_u8(const uint8_t *src, uint8_t *dst, uint8_t *tmp, int N, int H, int W, int oh, int ow,
+                  const int32_t *kx, const int32_t *bx, int ksx, const int32_t *ky, const int32_t *by, int ksy,
+                  int left, int top, int ow_c, int oh_c, int row0, int rows, g2s_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
