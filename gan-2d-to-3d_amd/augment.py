@@ -4,9 +4,14 @@ stylegan2-pytorch/non_leaking.py (`augment`, `random_apply_affine`, `random_appl
 
 A CUDA float32 image goes through two launches forward (g2s_ada_up2: reflect padding + 2x SYM6 upsampling;
 g2s_ada_warp_down: affine warp at double resolution + 2x SYM6 downsampling + colour matrix) and two backward, as ONE
-autograd node.  Its backward is once_differentiable: a double backward (R1 through the augmentation) raises.  G and
-C get no gradient, as in the reference.  With g2s_set_deterministic on, the backward raises (float-atomic scatter, no
-fixed-point variant).
+autograd node.  G and C get no gradient, as in the reference.
+
+`order=1` (the default): the node's backward is once_differentiable — a double backward raises — and with
+g2s_set_deterministic on it raises too (float-atomic scatter).  `order=2`: given its matrices the augmentation is affine
+in the image, y = L x + c, so its gradient L^T and the gradient of that, L, are the same kernels again: `_AdaFwd` and
+`_AdaAdj` are each other's backward and the result differentiates to any order (R1 through the augmentation).
+`_AdaAdj` takes the scatter while deterministic mode is off and the fixed-order gather
+(g2s_ada_warp_down_bwd_gather) while it is on.
 
 The matrices are sampled on the CPU from torch's global CPU generator, as the reference does, in the same order and
 with the same float32 arithmetic: equal seeds give equal G and C.  The pads and the matrix handed to the warp are
@@ -292,8 +297,115 @@ class _AdaFused(Function):
         return gx, None, None, None
 
 
-def _apply(img, G, C):
+def _bilinear_zeros(x, grid):
+    """F.grid_sample(x, grid, 'bilinear', 'zeros', align_corners=False) from gathers: torch's grid_sampler has no
+    derivative of its backward, a gather's backward (scatter_add) has one, and the sample is linear in x."""
+    B, C, H, W = x.shape
+    ix = ((grid[..., 0] + 1) * W - 1) / 2
+    iy = ((grid[..., 1] + 1) * H - 1) / 2
+    x0, y0 = ix.floor(), iy.floor()
+    flat = x.reshape(B, C, H * W)
+    out = 0
+    for dy in (0, 1):
+        for dx in (0, 1):
+            cx, cy = x0 + dx, y0 + dy
+            wgt = (1 - (ix - cx).abs()) * (1 - (iy - cy).abs())
+            inside = (cx >= 0) & (cx <= W - 1) & (cy >= 0) & (cy <= H - 1)
+            at = (cy.clamp(0, H - 1) * W + cx.clamp(0, W - 1)).long().reshape(B, 1, -1).expand(B, C, -1)
+            out = out + flat.gather(2, at) * (wgt * inside).reshape(B, 1, -1)
+    return out.reshape(B, C, *grid.shape[1:3])
+
+
+def _augment_twice(img, warp, pads, cmat):
+    """_augment_torch's arithmetic, step for step, with `_bilinear_zeros` for its grid_sample: differentiable twice
+    in img.  The order=2 route of CPU tensors and of dtypes the kernels do not take."""
+    B, C, H, W = img.shape
+    x0, x1, y0, y1 = pads
+    k = torch.tensor(SYM6).to(img)
+    x = F.pad(img, (x0, x1, y0, y1), mode="reflect").reshape(B * C, 1, H + y0 + y1, W + x0 + x1)
+    up = torch.stack((x, torch.zeros_like(x)), -1).flatten(-2)                       # zero insertion along x
+    x = F.conv2d(F.pad(up, (_TAPS // 2, _TAPS // 2 - 1)), k.flip(0).view(1, 1, 1, -1))
+    up = torch.stack((x, torch.zeros_like(x)), -2).flatten(-3, -2)                   # along y
+    x = F.conv2d(F.pad(up, (0, 0, _TAPS // 2, _TAPS // 2 - 1)), k.flip(0).view(1, 1, -1, 1))
+    x = x.view(B, C, x.shape[2], x.shape[3])
+    hs, ws = 2 * (H + 2 * _PAD_K), 2 * (W + 2 * _PAD_K)
+    grid = F.affine_grid(warp.to(x), (B, C, hs, ws), align_corners=False)
+    a = _bilinear_zeros(x, grid)
+    a = a.reshape(B * C, 1, hs, ws)[..., 1:-1, 1:-1]
+    a = F.conv2d(a, k.view(1, 1, 1, -1), stride=(1, 2))
+    a = F.conv2d(a, k.view(1, 1, -1, 1), stride=(2, 1))
+    y = a.view(B, C, H, W)
+    if cmat is not None:
+        cmat = cmat.to(y)
+        y = torch.einsum("bij,bjhw->bihw", cmat[:, :, :3], y) + cmat[:, :, 3].view(B, 3, 1, 1)
+    return y
+
+
+class _AdaFwd(Function):
+    """_AdaFused's forward as one half of a pair that differentiates to any order.  Given its matrices the map is
+    affine in the image, y = L img + c (c: the colour offset): its gradient is _AdaAdj, L^T."""
+
+    @staticmethod
+    def forward(ctx, img, warp, cmat, pads):
+        img = img.contiguous()
+        B, C, H, W = img.shape
+        x0, x1, y0, y1 = pads
+        H2, W2 = 2 * (H + y0 + y1), 2 * (W + x0 + x1)
+        L = _lib.load()
+        x2 = torch.empty((B, C, H2, W2), dtype=torch.float32, device=img.device)
+        _lib.check(L.g2s_ada_up2(_lib.ptr(img), _lib.ptr(x2), B, C, H, W, x0, x1, y0, y1, _lib.stream()))
+        y = torch.empty_like(img)
+        _lib.check(L.g2s_ada_warp_down(_lib.ptr(x2), _lib.ptr(warp), _lib.ptr(cmat), _lib.ptr(y), B, C, H, W, H2, W2,
+                                       _lib.stream()))
+        ctx.pads = pads
+        ctx.save_for_backward(warp, cmat)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        warp, cmat = ctx.saved_tensors
+        return _AdaAdj.apply(gy, warp, cmat, ctx.pads), None, None, None
+
+
+class _AdaAdj(Function):
+    """gy -> L^T gy: the warp adjoint and g2s_ada_up2_bwd.  The warp adjoint is the float-atomic scatter while
+    deterministic mode is off (the bits of _AdaFused's backward) and the fixed-order gather while it is on; the mode
+    is read when the node runs.  Its gradient is L: _AdaFwd without the colour offset."""
+
+    @staticmethod
+    def forward(ctx, gy, warp, cmat, pads):
+        gy = gy.contiguous()
+        B, C, H, W = gy.shape
+        x0, x1, y0, y1 = pads
+        H2, W2 = 2 * (H + y0 + y1), 2 * (W + x0 + x1)
+        L = _lib.load()
+        gx2 = torch.empty((B, C, H2, W2), dtype=torch.float32, device=gy.device)
+        if L.g2s_get_deterministic():
+            ga = torch.empty((B, C, 2 * (H + 2 * _PAD_K), 2 * (W + 2 * _PAD_K)), dtype=torch.float32, device=gy.device)
+            _lib.check(L.g2s_ada_warp_down_bwd_gather(_lib.ptr(gy), _lib.ptr(warp), _lib.ptr(cmat), _lib.ptr(gx2),
+                                                      _lib.ptr(ga), B, C, H, W, H2, W2, _lib.stream()))
+        else:
+            _lib.check(L.g2s_ada_warp_down_bwd(_lib.ptr(gy), _lib.ptr(warp), _lib.ptr(cmat), _lib.ptr(gx2), B, C, H, W,
+                                               H2, W2, 0, _lib.stream()))
+        gx = torch.empty_like(gy)
+        _lib.check(L.g2s_ada_up2_bwd(_lib.ptr(gx2), _lib.ptr(gx), B, C, H, W, x0, x1, y0, y1, _lib.stream()))
+        ctx.pads = pads
+        ctx.save_for_backward(warp, cmat)
+        return gx
+
+    @staticmethod
+    def backward(ctx, ggx):
+        warp, cmat = ctx.saved_tensors
+        if cmat is not None:
+            cmat = cmat.clone()
+            cmat[:, :, 3] = 0          # the linear part: the offset does not depend on the image
+        return _AdaFwd.apply(ggx, warp, cmat, ctx.pads), None, None, None
+
+
+def _apply(img, G, C, order=1):
     """The pipeline for given CPU matrices G [B, 3, 3] and C [B, 4, 4] or None."""
+    if order not in (1, 2):
+        raise ValueError(f"order is 1 (once differentiable) or 2 (differentiable to any order), got {order!r}")
     if img.dim() != 4 or img.shape[0] != G.shape[0]:
         raise ValueError(f"img [B, C, H, W] and G [B, 3, 3] must agree in B (got {tuple(img.shape)}, {tuple(G.shape)})")
     if C is not None and img.shape[1] != 3:
@@ -303,6 +415,10 @@ def _apply(img, G, C):
     pads = _pads(g_host, H, W, _TAPS)
     warp = _warp_matrix(g_host, pads, H, W)
     cmat = None if C is None else C.detach().float().cpu()[:, :3, :].contiguous()
+    if order == 2:
+        if not (img.is_cuda and img.dtype == torch.float32):
+            return _augment_twice(img, warp, pads, cmat)
+        return _AdaFwd.apply(img, warp.to(img.device), None if cmat is None else cmat.to(img.device), pads)
     if not img.is_cuda:
         return _augment_torch(img, warp, pads, cmat)
     if img.dtype != torch.float32:
@@ -311,19 +427,22 @@ def _apply(img, G, C):
 
 
 # ------------------------------------------------------------------------------------------ public functions
-def random_apply_affine(img, p, G=None, antialiasing_kernel=SYM6):
+def random_apply_affine(img, p, G=None, antialiasing_kernel=SYM6, order=1):
     """(warped image, G): G [B, 3, 3] maps output to input pixels about the image centre; None draws the inverse of
-    sample_affine(p, ...)."""
+    sample_affine(p, ...).  order: see augment."""
     if tuple(antialiasing_kernel) != SYM6:
         raise ValueError("only the SYM6 filter is built into the kernels")
     if G is None:
         G = torch.inverse(sample_affine(p, img.shape[0], img.shape[2], img.shape[3]))
-    return _apply(img, G, None), G
+    return _apply(img, G, None, order), G
 
 
-def random_apply_color(img, p, C=None):
+def random_apply_color(img, p, C=None, order=1):
     """(img with C [B, 4, 4] applied to its three channels, C); None draws sample_color(p, ...).  A single
-    elementwise expression in torch on either device; `augment` folds it into the warp's store instead."""
+    elementwise expression in torch on either device; `augment` folds it into the warp's store instead.  As a torch
+    expression it is differentiable to any order whichever `order` is given."""
+    if order not in (1, 2):
+        raise ValueError(f"order is 1 or 2, got {order!r}")
     if C is None:
         C = sample_color(p, img.shape[0])
     m = C.to(img)
@@ -331,12 +450,17 @@ def random_apply_color(img, p, C=None):
     return out, C
 
 
-def augment(img, p, transform_matrix=(None, None)):
+def augment(img, p, transform_matrix=(None, None), order=1):
     """(augmented image, (G, C)): random_apply_affine then random_apply_color, with the given matrices or fresh
-    draws (G first, then C, from torch's CPU generator).  One autograd node on the GPU."""
+    draws (G first, then C, from torch's CPU generator).  One autograd node on the GPU.
+
+    order=1: the node's backward is once_differentiable and refuses deterministic mode.  order=2: the node and its
+    gradient are each other's gradients (_AdaFwd / _AdaAdj), so the result differentiates to any order (R1 through the
+    augmentation), and its backward runs in deterministic mode, on the fixed-order gather; a CPU tensor or another
+    dtype takes the torch composition `_augment_twice`."""
     G, C = transform_matrix
     if G is None:
         G = torch.inverse(sample_affine(p, img.shape[0], img.shape[2], img.shape[3]))
     if C is None:
         C = sample_color(p, img.shape[0])
-    return _apply(img, G, C), (G, C)
+    return _apply(img, G, C, order), (G, C)

@@ -16,7 +16,11 @@
 //   ada_warp_down_bwd  gy -> gx2, the exact adjoint: a workgroup owns a 32x32 tile of A's gradient, gathers it from
 //                      the 22x22 tile of (Cmat^T gy) that reaches it (6 taps per axis and parity) and scatters the
 //                      bilinear adjoint with float atomics.
-//   ada_up2_bwd        gx2 -> gx, the exact adjoint: gP[q] = sum_u k[11-u] gx2[2q+6-u] per axis (a 12-tap stride-2
+//   ada_down_bwd +     the same adjoint as a gather (g2s_ada_warp_down_bwd_gather): the first half of the above with
+//   ada_warp_gather    A's gradient stored to a workspace, then one thread per gx2 element that walks the bounding
+//                      box of the pre-image of its 2x2 neighbourhood under the affine map and sums, rows outer and
+//                      columns inner, the forward's own bilinear weight times A's gradient.  No atomics, no clear.
+//   ada_up2_bwd       gx2 -> gx, the exact adjoint: gP[q] = sum_u k[11-u] gx2[2q+6-u] per axis (a 12-tap stride-2
 //                      pass), and gx[i] sums gP over the padded positions that reflect onto i — the direct one and up
 //                      to one mirror image per side and axis.  Gathered per mirror image, no atomics.
 //
@@ -24,9 +28,10 @@
 //
 // Deterministic mode (g2s_set_deterministic): ada_warp_down_bwd scatters with float atomics whose order
 // varies from run to run and has NO fixed-point variant — it REFUSES with G2S_ERR_INVALID while the mode is on.
-// The other three kernels have one fixed summation order and run in either mode with the same bits.
+// Every other kernel has one fixed summation order and runs in either mode with the same bits; the gather pair is
+// the adjoint to call while the mode is on (augment.py's _AdaAdj reads the mode when it runs).
 //
-// Roofline class: all four are HBM/L2-bound streaming passes with ~150-300 flops per output element from LDS;
+// Roofline class: the four fused kernels are HBM/L2-bound streaming passes with ~150-300 flops per output element from LDS;
 // see DESIGN.md 4.20.
 #include "g2s_common.h"
 
@@ -304,6 +309,134 @@ __global__ __launch_bounds__(256) void ada_warp_down_bwd(const float *__restrict
     }
 }
 
+// The first half of ada_warp_down_bwd (Cmat^T gy, then the two 6-taps-per-parity passes) with A's gradient stored:
+// ga [B, C, Hs, Ws], every element written exactly once.  Same tiling, same order of operations.
+// grid (cdiv(Ws, 32), cdiv(Hs, 32), COLOR ? B : B*C)
+template <bool COLOR>
+__global__ __launch_bounds__(256) void ada_down_bwd(const float *__restrict__ gy, const float *__restrict__ Cmat,
+                                                    float *__restrict__ ga_out, AdaWarp d) {
+    __shared__ float gz[WB_G][WB_G + 1];
+    __shared__ float tmp[WB_T][WB_G + 1];
+    const int tid = threadIdx.x;
+    const int i0 = blockIdx.y * WB_T, j0 = blockIdx.x * WB_T, nb = i0 / 2 - 6, mb = j0 / 2 - 6;
+    const int b = COLOR ? blockIdx.z : blockIdx.z / d.C, ch0 = COLOR ? 0 : blockIdx.z % d.C;
+    const int Hs = 2 * (d.H + 6), Ws = 2 * (d.W + 6);
+    const size_t hw = (size_t)d.H * d.W;
+    for (int cc = 0; cc < (COLOR ? 3 : 1); cc++) {
+        if (cc) __syncthreads();
+        for (int e = tid; e < WB_G * WB_G; e += 256) {
+            const int ln = e / WB_G, lm = e % WB_G, n = nb + ln, m = mb + lm;
+            float v = 0.0f;
+            if (n >= 0 && n < d.H && m >= 0 && m < d.W) {
+                const float *gp = gy + (size_t)b * d.C * hw + (size_t)n * d.W + m;
+                if (COLOR) {
+                    const float *cm = Cmat + b * 12 + cc;
+                    v = cm[0] * gp[0] + cm[4] * gp[hw] + cm[8] * gp[2 * hw];
+                } else {
+                    v = gp[ch0 * hw];
+                }
+            }
+            gz[ln][lm] = v;
+        }
+        __syncthreads();
+        for (int e = tid; e < WB_T * WB_G; e += 256) {
+            const int li = e / WB_G, lm = e % WB_G, s0 = (li & 1) ? 0 : 1;
+            float acc = 0.0f;
+#pragma unroll
+            for (int q = 0; q < 6; q++) {
+                const int s = s0 + 2 * q;
+                acc += ADA_K[s] * gz[(li - 1 - s) / 2 + 6][lm];
+            }
+            tmp[li][lm] = acc;
+        }
+        __syncthreads();
+        float *ap = ga_out + ((size_t)b * d.C + ch0 + cc) * Hs * Ws;
+        for (int e = tid; e < WB_T * WB_T; e += 256) {
+            const int li = e >> 5, lj = e & 31, i = i0 + li, j = j0 + lj, s0 = (lj & 1) ? 0 : 1;
+            if (i >= Hs || j >= Ws) continue;
+            float ga = 0.0f;
+#pragma unroll
+            for (int q = 0; q < 6; q++) {
+                const int s = s0 + 2 * q;
+                ga += ADA_K[s] * tmp[li][(lj - 1 - s) / 2 + 6];
+            }
+            ap[(size_t)i * Ws + j] = ga;
+        }
+    }
+}
+
+constexpr int GA_TX = 32, GA_TY = 8;   // gx2 positions per workgroup
+
+// The bilinear adjoint as a gather: one thread per gx2[b, c, sy, sx], one fixed summation order, no atomics.
+//
+// In exact arithmetic bilin_of's sample position is affine in A's position (i, j):
+//   ix = jxx j + jxy i + ox,   iy = jyx j + jyy i + oy,
+//   jxx = t0 W2 / Ws, jxy = t1 W2 / Hs, jyx = t3 H2 / Ws, jyy = t4 H2 / Hs.
+// A's position (i, j) has (sy, sx) among its four corners only if |ix - sx| < 1 and |iy - sy| < 1.  bilin_of
+// computes ix in float32: four roundings of values no larger than about (|t0| + |t1| + |t2| + 1) W2, hence the
+// slack `sl` on the square's half side (4 ulp of that magnitude, 1.2e-7 each).  The pre-image of the square
+// under the inverse Jacobian is a parallelogram; its bounding box, widened by one position per side and clipped
+// to A, holds every candidate.  The weight of a candidate comes from bilin_of itself — the forward's own float32
+// weights, so this is the transpose of what the forward applies — and a candidate whose corners miss (sy, sx)
+// adds nothing.  A singular or near-singular matrix (or a non-finite one) makes the box all of A: slow, and
+// neither wrong nor unbounded.  The box is computed in double: at sides of 32768 a float32 pre-image would
+// itself be off by more than the one position of widening.
+// grid (cdiv(W2, 32), cdiv(H2, 8), B*C)
+__global__ __launch_bounds__(256) void ada_warp_gather(const float *__restrict__ ga, const float *__restrict__ Ginv,
+                                                       float *__restrict__ gx2, AdaWarp d) {
+    __shared__ double inv[8];   // inverse Jacobian (4), offsets ox, oy, half extents of the box in j and i
+    const int tid = threadIdx.x;
+    const int b = blockIdx.z / d.C;
+    const int Hs = 2 * (d.H + 6), Ws = 2 * (d.W + 6);
+    float t[6];
+#pragma unroll
+    for (int q = 0; q < 6; q++) t[q] = Ginv[b * 6 + q];
+    if (tid == 0) {
+        const double w2 = d.W2, h2 = d.H2, ws = Ws, hs = Hs;
+        const double jxx = t[0] * w2 / ws, jxy = t[1] * w2 / hs, jyx = t[3] * h2 / ws, jyy = t[4] * h2 / hs;
+        const double ox = ((t[0] * (1.0 / ws - 1.0) + t[1] * (1.0 / hs - 1.0) + t[2] + 1.0) * w2 - 1.0) * 0.5;
+        const double oy = ((t[3] * (1.0 / ws - 1.0) + t[4] * (1.0 / hs - 1.0) + t[5] + 1.0) * h2 - 1.0) * 0.5;
+        const double det = jxx * jyy - jxy * jyx;
+        const double slx = 1.0 + 4.8e-7 * (fabs((double)t[0]) + fabs((double)t[1]) + fabs((double)t[2]) + 1.0) * w2;
+        const double sly = 1.0 + 4.8e-7 * (fabs((double)t[3]) + fabs((double)t[4]) + fabs((double)t[5]) + 1.0) * h2;
+        // [j; i] = inv ([ix; iy] - [ox; oy])
+        const double a = jyy / det, bb = -jxy / det, c = -jyx / det, dd = jxx / det;
+        inv[0] = a; inv[1] = bb; inv[2] = c; inv[3] = dd; inv[4] = ox; inv[5] = oy;
+        inv[6] = fabs(a) * slx + fabs(bb) * sly + 1.0;
+        inv[7] = fabs(c) * slx + fabs(dd) * sly + 1.0;
+    }
+    __syncthreads();
+    const int sx = blockIdx.x * GA_TX + (tid & (GA_TX - 1)), sy = blockIdx.y * GA_TY + tid / GA_TX;
+    if (sx >= d.W2 || sy >= d.H2) return;
+    int jlo = 0, jhi = Ws - 1, ilo = 0, ihi = Hs - 1;
+    const double ej = inv[6], ei = inv[7];
+    const double rx = (double)sx - inv[4], ry = (double)sy - inv[5];
+    const double pj = inv[0] * rx + inv[1] * ry, pi = inv[2] * rx + inv[3] * ry;
+    // anything non-finite or wider than A fails these tests and keeps the whole range
+    if (ej < (double)Ws && fabs(pj) < 1e9) {
+        jlo = (int)fmax(floor(pj - ej), 0.0);
+        jhi = (int)fmin(ceil(pj + ej), (double)(Ws - 1));
+    }
+    if (ei < (double)Hs && fabs(pi) < 1e9) {
+        ilo = (int)fmax(floor(pi - ei), 0.0);
+        ihi = (int)fmin(ceil(pi + ei), (double)(Hs - 1));
+    }
+    const float *ap = ga + (size_t)blockIdx.z * Hs * Ws;
+    float acc = 0.0f;
+    for (int i = ilo; i <= ihi; i++) {
+        for (int j = jlo; j <= jhi; j++) {
+            const Bilin c = bilin_of(i, j, t, d);
+            const int dx = sx - c.x0, dy = sy - c.y0;
+            if ((dx | dy) & ~1) continue;   // (sy, sx) is none of the four corners
+            const bool in_x = dx ? c.in_x1 : c.in_x0, in_y = dy ? c.in_y1 : c.in_y0;
+            if (!(in_x && in_y)) continue;
+            const float w = dy ? (dx ? c.se : c.sw) : (dx ? c.ne : c.nw);
+            acc += __fmul_rn(w, ap[(size_t)i * Ws + j]);   // the scatter's product, rounded before it is added
+        }
+    }
+    gx2[(size_t)blockIdx.z * d.H2 * d.W2 + (size_t)sy * d.W2 + sx] = acc;
+}
+
 static int up_check(const char *what, int B, int C, int H, int W, int px0, int px1, int py0, int py1) {
     G2S_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "%s: sizes must be positive", what);
     G2S_REQUIRE(px0 >= 0 && px1 >= 0 && py0 >= 0 && py1 >= 0, "%s: pads must be non-negative", what);
@@ -372,4 +505,21 @@ extern "C" int g2s_ada_warp_down_bwd(const float *gy, const float *Ginv, const f
     if (Cmat) ada_warp_down_bwd<true><<<g, 256, 0, as_stream(stream)>>>(gy, Ginv, Cmat, gx2, d);
     else ada_warp_down_bwd<false><<<g, 256, 0, as_stream(stream)>>>(gy, Ginv, nullptr, gx2, d);
     return check_launch("g2s_ada_warp_down_bwd");
+}
+
+extern "C" int g2s_ada_warp_down_bwd_gather(const float *gy, const float *Ginv, const float *Cmat, float *gx2,
+                                            float *ga, int B, int C, int H, int W, int H2, int W2,
+                                            g2s_stream_t stream) {
+    G2S_REQUIRE(gy && Ginv && gx2 && ga, "g2s_ada_warp_down_bwd_gather: NULL pointer argument (only Cmat may be NULL)");
+    int rc = warp_check("g2s_ada_warp_down_bwd_gather", Cmat, B, C, H, W, H2, W2);
+    if (rc) return rc;
+    hipStream_t st = as_stream(stream);
+    const AdaWarp d{C, H, W, H2, W2};
+    const dim3 g1(cdiv(2 * (W + 6), WB_T), cdiv(2 * (H + 6), WB_T), Cmat ? B : B * C);
+    if (Cmat) ada_down_bwd<true><<<g1, 256, 0, st>>>(gy, Cmat, ga, d);
+    else ada_down_bwd<false><<<g1, 256, 0, st>>>(gy, nullptr, ga, d);
+    rc = check_launch("g2s_ada_warp_down_bwd_gather (down)");
+    if (rc) return rc;
+    ada_warp_gather<<<dim3(cdiv(W2, GA_TX), cdiv(H2, GA_TY), B * C), 256, 0, st>>>(ga, Ginv, gx2, d);
+    return check_launch("g2s_ada_warp_down_bwd_gather");
 }

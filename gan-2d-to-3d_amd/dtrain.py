@@ -12,10 +12,11 @@ tensors or other dtypes the reference's torch composition.  The backward of the 
 torch.mul: one elementwise launch over B x n that a kernel of ours would not make cheaper.
 
 `DiscriminatorTrainer.step` runs the discriminator under `conv2d_gradfix.use()`: trainable, twice-differentiable
-convolutions and the one-launch minibatch stddev.  `augment.augment` is once differentiable, so the R1 pass with
-augmentation — one step in `d_reg_every` — takes a torch composition of the same arithmetic on the matrices
-`sample_affine` / `sample_color` draw.  `augment._augment_torch` cannot serve as it stands: torch's grid_sampler
-backward has no derivative, so `_augment_twice` restates it with the bilinear sample written as gathers."""
+convolutions and the one-launch minibatch stddev.  The R1 pass with augmentation — one step in `d_reg_every` —
+differentiates the augmentation twice: it takes `augment(..., order=2)`, whose node and gradient node are each other's
+gradients on the kernels of csrc/ada.hip.  CPU tensors take `augment._augment_twice`, a torch composition with the
+bilinear sample written as gathers (torch's grid_sampler backward has no derivative).  `--deterministic` switches
+libg2s to its fixed-order routes before the first step."""
 import argparse
 import math
 import os
@@ -134,54 +135,16 @@ class _Ada(_aug.AdaptiveAugment):
         return self.ada_aug_p
 
 
-def _bilinear_zeros(x, grid):
-    """F.grid_sample(x, grid, 'bilinear', 'zeros', align_corners=False) from gathers: torch's grid_sampler has no
-    derivative of its backward, a gather's backward (scatter_add) has one, and the sample is linear in x."""
-    B, C, H, W = x.shape
-    ix = ((grid[..., 0] + 1) * W - 1) / 2
-    iy = ((grid[..., 1] + 1) * H - 1) / 2
-    x0, y0 = ix.floor(), iy.floor()
-    flat = x.reshape(B, C, H * W)
-    out = 0
-    for dy in (0, 1):
-        for dx in (0, 1):
-            cx, cy = x0 + dx, y0 + dy
-            wgt = (1 - (ix - cx).abs()) * (1 - (iy - cy).abs())
-            inside = (cx >= 0) & (cx <= W - 1) & (cy >= 0) & (cy <= H - 1)
-            at = (cy.clamp(0, H - 1) * W + cx.clamp(0, W - 1)).long().reshape(B, 1, -1).expand(B, C, -1)
-            out = out + flat.gather(2, at) * (wgt * inside).reshape(B, 1, -1)
-    return out.reshape(B, C, *grid.shape[1:3])
+_bilinear_zeros = _aug._bilinear_zeros
+_augment_twice = _aug._augment_twice          # the torch composition; it lives beside the nodes it restates
 
 
-def _augment_twice(img, warp, pads, cmat):
-    """augment._augment_torch's arithmetic, step for step, with `_bilinear_zeros` for its grid_sample: differentiable
-    twice in img."""
-    B, C, H, W = img.shape
-    x0, x1, y0, y1 = pads
-    taps = _aug._TAPS
-    k = torch.tensor(_aug.SYM6).to(img)
-    x = F.pad(img, (x0, x1, y0, y1), mode="reflect").reshape(B * C, 1, H + y0 + y1, W + x0 + x1)
-    up = torch.stack((x, torch.zeros_like(x)), -1).flatten(-2)                       # zero insertion along x
-    x = F.conv2d(F.pad(up, (taps // 2, taps // 2 - 1)), k.flip(0).view(1, 1, 1, -1))
-    up = torch.stack((x, torch.zeros_like(x)), -2).flatten(-3, -2)                   # along y
-    x = F.conv2d(F.pad(up, (0, 0, taps // 2, taps // 2 - 1)), k.flip(0).view(1, 1, -1, 1))
-    x = x.view(B, C, x.shape[2], x.shape[3])
-    hs, ws = 2 * (H + 2 * _aug._PAD_K), 2 * (W + 2 * _aug._PAD_K)
-    grid = F.affine_grid(warp.to(x), (B, C, hs, ws), align_corners=False)
-    a = _bilinear_zeros(x, grid)
-    a = a.reshape(B * C, 1, hs, ws)[..., 1:-1, 1:-1]
-    a = F.conv2d(a, k.view(1, 1, 1, -1), stride=(1, 2))
-    a = F.conv2d(a, k.view(1, 1, -1, 1), stride=(2, 1))
-    y = a.view(B, C, H, W)
-    if cmat is not None:
-        cmat = cmat.to(y)
-        y = torch.einsum("bij,bjhw->bihw", cmat[:, :, :3], y) + cmat[:, :, 3].view(B, 3, 1, 1)
-    return y
-
-
-def augment_differentiable(img, p, transform_matrix=(None, None)):
-    """augment.augment's result on either device in torch ops that can be differentiated twice (the R1 pass):
-    the same draws, pads and matrices, `augment._augment_torch`'s arithmetic (`_augment_twice`)."""
+def augment_differentiable(img, p, transform_matrix=(None, None), composed=False):
+    """augment.augment's result in a form that can be differentiated twice (the R1 pass), with the same draws, pads
+    and matrices: `augment(..., order=2)` — on a CUDA float32 image the node pair of csrc/ada.hip, else the torch
+    composition `_augment_twice`.  composed=True forces the composition on any tensor (measurements, cross-checks)."""
+    if not composed:
+        return _aug.augment(img, p, transform_matrix, order=2)
     G, C = transform_matrix
     if G is None:
         G = torch.inverse(_aug.sample_affine(p, img.shape[0], img.shape[2], img.shape[3]))
@@ -330,6 +293,8 @@ def build_parser():
     parser.add_argument("--r1", type=float, default=10)
     parser.add_argument("--d-reg-every", dest="d_reg_every", type=int, default=16)
     parser.add_argument("--seed", type=int, default=0)
+    parser.add_argument("--deterministic", action="store_true",
+                        help="fixed-order kernels throughout (lib.set_deterministic): reproducible, slower")
     parser.add_argument("--log-every", dest="log_every", type=int, default=100)
     parser.add_argument("--device", default="cuda")
     parser.add_argument("--out", required=True)
@@ -342,6 +307,8 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     device = torch.device(args.device)
     torch.manual_seed(args.seed)
+    if args.deterministic:
+        _lib.set_deterministic(True)
     ckpt = torch.load(args.ckpt, map_location="cpu", weights_only=True)
     g_ema = Generator(args.size, 512, 8, channel_multiplier=args.channel_multiplier)
     g_ema.load_state_dict(ckpt["g_ema"], strict=False)

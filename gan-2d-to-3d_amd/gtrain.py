@@ -201,7 +201,8 @@ class GeneratorTrainer:
                 noise = mixing_noise(self.batch, latent_dim, self.mixing, self.device)
             fake_img, _ = self.g(noise, noise=maps)
             if self.augment:
-                fake_img, _ = _aug.augment(fake_img, self.ada_aug_p)
+                # order=2: the same four kernels while deterministic mode is off, the fixed-order adjoint while on
+                fake_img, _ = _aug.augment(fake_img, self.ada_aug_p, order=2)
             fake_pred = _pred(self.d(fake_img))
             g_loss = g_nonsaturating_loss(fake_pred)
             loss = {"g": g_loss.detach()}

@@ -133,6 +133,7 @@ SIGNATURES = {
     "g2s_ada_up2_bwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "g2s_ada_warp_down": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "g2s_ada_warp_down_bwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "g2s_ada_warp_down_bwd_gather": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "g2s_mbstd_fwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     "g2s_mbstd_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "g2s_mbstd_bwd2": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),

@@ -3,7 +3,7 @@
 
     python -m gan2shape_amd.train --size 128 --channel-multiplier 1 --data root/car --iter 2000 --batch 16 \
         [--ckpt G_D.pt] [--augment] [--mixing 0.9] [--path-regularize 2] [--g-reg-every 4] [--save-every 10000] \
-        --out ckpts/train.pt
+        [--deterministic] --out ckpts/train.pt
 
 The checkpoint has train.py's keys: g, d, g_ema, g_optim, d_optim, ada_aug_p.  Without --ckpt the weights are fresh
 (torch.manual_seed(--seed)) and g_ema starts as a copy of g (train.py:419-421).  Not built: distributed training,
@@ -43,6 +43,8 @@ def build_parser():
     parser.add_argument("--ada-target", dest="ada_target", type=float, default=0.6)
     parser.add_argument("--ada-length", dest="ada_length", type=int, default=500_000)
     parser.add_argument("--seed", type=int, default=0)
+    parser.add_argument("--deterministic", action="store_true",
+                        help="fixed-order kernels throughout (lib.set_deterministic): reproducible, slower")
     parser.add_argument("--log-every", dest="log_every", type=int, default=100)
     parser.add_argument("--save-every", dest="save_every", type=int, default=10000,
                         help="also write --out every this many iterations (train.py: 10000); 0: only at the end")
@@ -101,6 +103,9 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     device = torch.device(args.device)
     torch.manual_seed(args.seed)
+    if args.deterministic:
+        from . import lib
+        lib.set_deterministic(True)
     dt, gt = build_trainers(args, device)
     reals = dtrain.batches(args.data, args.size, args.batch, torch.Generator().manual_seed(args.seed), device)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -958,6 +958,12 @@ int g2s_depth_metrics(const float *depth_pred, const float *depth_gt, const floa
  * g2s_ada_warp_down_bwd: gy [B, C, H, W] -> gx2 [B, C, H2, W2], the adjoint of the above in x2 (Cmat transposed).
  *   Float atomics into gx2, which the call clears first unless acc_is_zero = 1 says it is zero already.  There is
  *   no fixed-point variant: in deterministic mode (g2s_set_deterministic) the call returns G2S_ERR_INVALID.
+ * g2s_ada_warp_down_bwd_gather: the same adjoint as a gather, in two launches.  ga [B, C, 2 (H + 6), 2 (W + 6)] is a
+ *   caller-provided workspace that receives the gradient of A (every element written once); then every gx2[b, c, sy, sx]
+ *   sums, in one fixed order (A's rows outer, columns inner), weight * ga over the positions of A whose bilinear
+ *   footprint holds (sy, sx) — the weights are those of the forward's own sample routine.  No atomics, every element
+ *   of gx2 is written (no clear needed), and the bits do not depend on g2s_set_deterministic: it runs in either mode.
+ *   It differs from g2s_ada_warp_down_bwd in summation order only.
  * g2s_ada_up2_bwd: gx2 -> gx [B, C, H, W], the adjoint of g2s_ada_up2 (mirror images gathered, no atomics; every
  *   element of gx is written).
  * Ginv and Cmat get no gradient.  B * C <= 65535, H, W <= 16384.  Every check precedes the first launch; nothing
@@ -971,6 +977,8 @@ int g2s_ada_warp_down(const float *x2, const float *Ginv, const float *Cmat, flo
                       int H2, int W2, g2s_stream_t stream);
 int g2s_ada_warp_down_bwd(const float *gy, const float *Ginv, const float *Cmat, float *gx2, int B, int C, int H,
                           int W, int H2, int W2, int acc_is_zero, g2s_stream_t stream);
+int g2s_ada_warp_down_bwd_gather(const float *gy, const float *Ginv, const float *Cmat, float *gx2, float *ga, int B,
+                                 int C, int H, int W, int H2, int W2, g2s_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------
  * Discriminator training (csrc/dtrain.hip): minibatch stddev, logistic loss, R1 penalty.  f32, fixed summation
