@@ -50,6 +50,7 @@ SOURCES = {
     "dtrain.hip": [],
     "gtrain.hip": [],
     "dataprep.hip": [],
+    "mirror.hip": [],
     "probe.hip": [],
 }
 # The kernels take their descriptor struct by value.  Clang copies such a parameter into a private

@@ -245,6 +245,64 @@ class DepthHeadFunction(Function):
         return g_raw, None, None, None, None, None
 
 
+class MirrorPairFunction(Function):
+    """The symmetry pair of a flipped step (model.py forward_step1 / forward_step3 with flip1 / flip3): for the depth
+    [N,H,W] (or [N,1,H,W]) and the albedo [N,C,H,W] of one step, `repeat` copies of every sample followed by `repeat`
+    copies of its left-right mirror — cat([x.repeat_interleave(repeat, 0), x.flip(-1).repeat_interleave(repeat, 0)])
+    for both tensors in ONE launch each way (csrc/mirror.hip).  The backward gathers in a fixed order without atomics;
+    it is not differentiable a second time."""
+
+    @staticmethod
+    def forward(ctx, depth, albedo, repeat):
+        d, a = _f32c(depth), (None if albedo is None else _f32c(albedo))
+        N, (H, W) = d.shape[0], d.shape[-2:]
+        Cd = d.numel() // (N * H * W)
+        if a is not None and (a.dim() != 4 or a.shape[0] != N or tuple(a.shape[-2:]) != (H, W)):
+            raise ValueError(f"mirror_pair: depth {tuple(d.shape)} and albedo {tuple(a.shape)} must share N, H, W")
+        d2 = torch.empty((2 * N * repeat,) + tuple(d.shape[1:]), dtype=torch.float32, device=d.device)
+        a2 = None if a is None else torch.empty((2 * N * repeat,) + tuple(a.shape[1:]), dtype=torch.float32, device=a.device)
+        _lib.check(_lib.load().g2s_mirror_pair_fwd(_lib.ptr(d), _lib.ptr(d2), Cd, _lib.ptr(a), _lib.ptr(a2),
+                                                   0 if a is None else a.shape[1], N, H, W, repeat, _lib.stream()))
+        ctx.meta = (tuple(d.shape), None if a is None else tuple(a.shape), Cd, repeat)
+        # an output follows ITS input: step 1 detaches the depth, and a depth2 that asked for a gradient because the
+        # albedo does would drag the whole geometry chain (normals, warp, rasterizer) through backward for nothing
+        dead = [y for y, need in ((d2, ctx.needs_input_grad[0]), (a2, ctx.needs_input_grad[1])) if y is not None and not need]
+        if dead:
+            ctx.mark_non_differentiable(*dead)
+        return d2, a2
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gd2, ga2):
+        dshape, ashape, Cd, repeat = ctx.meta
+        N, (H, W) = dshape[0], dshape[-2:]
+        # an output that took no part in the loss arrives as None: the launch runs on the gradients that are there
+        # (its first slot takes either tensor, its second is optional)
+        slots = [(name, _f32c(g), shape, C) for name, g, shape, C, need in
+                 (("depth", gd2, dshape, Cd, ctx.needs_input_grad[0]),
+                  ("albedo", ga2, ashape, ashape[1] if ashape else 0, ctx.needs_input_grad[1]))
+                 if g is not None and shape is not None and need]
+        if not slots:
+            return None, None, None
+        grads, args = {}, []
+        for name, g, shape, C in slots:
+            grads[name] = torch.empty(shape, dtype=torch.float32, device=g.device)
+            args += [_lib.ptr(g), _lib.ptr(grads[name]), C]
+        if len(slots) == 1:
+            args += [None, None, 0]
+        _lib.check(_lib.load().g2s_mirror_pair_bwd(*args, N, H, W, repeat, _lib.stream()))
+        return grads.get("depth"), grads.get("albedo"), None
+
+
+def mirror_pair(depth, albedo=None, repeat=1):
+    """(depth2, albedo2): rows [x[0] x repeat, .., x[N-1] x repeat, mirror(x[0]) x repeat, ..] of both tensors."""
+    repeat = int(repeat)
+    if repeat < 1:
+        raise ValueError("mirror_pair: repeat must be at least 1")
+    _lib.require_cuda(depth, albedo)
+    return MirrorPairFunction.apply(depth, albedo, repeat)
+
+
 def depth_head(raw, W, lo, hi, clamp_border, border_depth):
     return DepthHeadFunction.apply(raw, W, lo, hi, clamp_border, border_depth)
 

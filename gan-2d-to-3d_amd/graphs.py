@@ -15,6 +15,11 @@ aborts.
 
 Static buffers: `image`, `latent` (copy a new image in to reuse the graphs), and the `collected`
 hand-offs — graph k+1 reads the output tensors of graph k in place.
+
+Symmetry flips: a captured step 1 / step 3 depends on the model's flip switch (flip1 / flip3: twice the rows
+behind the nets), so the graphs are keyed by (kind, flip) and a schedule whose stages differ captures each variant
+once.  `loss[kind]` and `collected[kind]` stay the hand-off buffers of the FIRST variant captured for a kind (the
+graphs of the next kind read them in place); another variant's outputs are copied into them after its replay.
 """
 import torch
 
@@ -31,6 +36,7 @@ class GraphedSteps:
         self.loss = {}
         self.collected = {1: None, 2: None, 3: None}
         self._static_src = {}
+        self._outputs = {}      # (kind, flip) -> (loss, collected): the static outputs of that captured graph
         self.warmup = warmup
         for opt in (trainer.optim_step1, trainer.optim_step2, trainer.optim_step3):
             for group in opt.param_groups:
@@ -49,6 +55,23 @@ class GraphedSteps:
 
     def _source(self, kind):
         return {1: None, 2: self.collected[1], 3: self.collected[2]}[kind]
+
+    def key(self, kind):
+        """(kind, flip): what a captured iteration of `kind` depends on besides the static buffers."""
+        flip = {1: 'flip1', 3: 'flip3'}.get(kind)
+        return kind, bool(getattr(self.model, flip, False)) if flip else False
+
+    def captured(self, kind):
+        return self.key(kind) in self.graphs
+
+    def _publish(self, kind, loss, collected):
+        """Copy a variant's outputs into the kind's hand-off buffers (no-op for the variant that owns them)."""
+        with torch.no_grad():
+            if loss is not self.loss[kind]:
+                self.loss[kind].copy_(loss.detach())
+            for dst, srct in zip(self.collected[kind] or (), collected or ()):
+                if torch.is_tensor(dst) and dst is not srct:
+                    dst.copy_(srct.detach())
 
     def capture(self, kind, warmup=None):
         """Warm up `warmup` (default: the constructor's) eager iterations on a side stream (library
@@ -81,18 +104,16 @@ class GraphedSteps:
                 warm_loss, warm_collected = self._iteration(kind, src)
         torch.cuda.current_stream().wait_stream(s)
         optim.zero_grad(set_to_none=True)
-        self.graphs[kind], loss, collected = self._record(kind, src)
-        self.loss[kind] = loss.detach()
-        self.collected[kind] = collected
+        key = self.key(kind)
+        self.graphs[key], loss, collected = self._record(kind, src)
+        self._outputs[key] = (loss.detach(), collected)
+        if not any(k[0] == kind for k in self._outputs if k != key):   # the first variant owns the hand-off buffers
+            self.loss[kind], self.collected[kind] = self._outputs[key]
         # A capture records, it does not run: the graph's static outputs (the loss, the hand-off
         # to the next step kind) are filled with the results of the last warm-up iteration, so they
         # are valid even if no replay follows (a block that asks for no more than `warmup`
         # iterations).
-        with torch.no_grad():
-            self.loss[kind].copy_(warm_loss.detach())
-            for dst, srct in zip(collected or (), warm_collected or ()):
-                if torch.is_tensor(dst):
-                    dst.copy_(srct.detach())
+        self._publish(kind, warm_loss, warm_collected)
         return warmup  # iterations actually executed
 
     def _record(self, kind, src):
@@ -104,7 +125,9 @@ class GraphedSteps:
 
     def run(self, kind):
         """One training iteration of kind `kind` (graph replay)."""
-        self.graphs[kind].replay()
+        key = self.key(kind)
+        self.graphs[key].replay()
+        self._publish(kind, *self._outputs[key])
         return self.loss[kind]
 
     def set_sample(self, image, latent):
@@ -163,10 +186,12 @@ class GraphedJointSteps(GraphedSteps):
         return (a, b), loss, collected
 
     def run(self, kind):
-        a, b = self.graphs[kind]
+        key = self.key(kind)
+        a, b = self.graphs[key]
         a.replay()
         self.buckets[kind].all_reduce_mean()
         b.replay()
+        self._publish(kind, *self._outputs[key])
         return self.loss[kind]
 
     def set_source(self, kind, collected):

@@ -147,6 +147,8 @@ SIGNATURES = {
     "g2s_ema_accumulate": (_i, [_p, _p, _i, _i, _f, _f, _p]),
     "g2s_u8_batch": (_i, [_p, _i64, _p, _p, _p, _i, _i, _p]),
     "g2s_resize_u8": (_i, [_p, _p, _p] + [_i] * 5 + [_p, _p, _i, _p, _p, _i] + [_i] * 6 + [_p]),
+    "g2s_mirror_pair_fwd": (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "g2s_mirror_pair_bwd": (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p]),
 }
 
 

@@ -50,7 +50,7 @@ def weighted_total(terms):
     per_elem = [tuple(float(v) for v in w) if isinstance(w, (tuple, list)) else (float(w) / f.numel(),) * f.numel()
                 for (w, _), f in zip(terms, flat)]
     assert all(len(pe) == f.numel() for pe, f in zip(per_elem, flat))
-    key = (tuple(per_elem), flat[0].device)
+    key = (tuple(per_elem), flat[0].device) if flat[0].dtype == torch.float32 else (tuple(per_elem), flat[0].device, flat[0].dtype)
     wv = _WSUM_CONST.get(key)
     if wv is None:
         if flat[0].is_cuda and torch.cuda.is_current_stream_capturing():
@@ -58,12 +58,19 @@ def weighted_total(terms):
             raise RuntimeError("weighted_total: first use of this weight vector under graph capture; run the step eagerly once")
         if len(_WSUM_CONST) > 64:
             _WSUM_CONST.clear()
-        wv = _WSUM_CONST[key] = torch.tensor([v for pe in per_elem for v in pe], dtype=torch.float32).to(flat[0].device)
+        wv = _WSUM_CONST[key] = torch.tensor([v for pe in per_elem for v in pe], dtype=flat[0].dtype).to(flat[0].device)
     return torch.dot(torch.cat(flat), wv)
 
 
 class GAN2Shape(nn.Module):
     NETS = ['lighting', 'viewpoint', 'depth', 'albedo', 'offset_encoder']
+    # the symmetry assumption (added; the reference marks the place with `TODO: add flips?`, model.py:102,124): with
+    # flip1 (step 1) / flip3 (step 3 and its inner step-1 pass) on, the canonical depth and albedo are rendered a second
+    # time mirrored left-right under the same view and light, and that reconstruction is held to the same target with
+    # weight lam_flip.  The trainers set the two switches per stage from the config's flip1_cfg / flip3_cfg.
+    flip1 = False
+    flip3 = False
+    lam_flip = 0.5
 
     def __init__(self, config, debug=False, device="cuda"):
         super().__init__()
@@ -123,6 +130,7 @@ class GAN2Shape(nn.Module):
         self.lam_perc = 1
         self.lam_smooth = 0.01
         self.lam_regular = 0.01
+        self.lam_flip = config.get('lam_flip', 0.5)
         self.xyz_rotation_range = config.get('xyz_rotation_range', 60)
         self.xy_translation_range = config.get('xy_translation_range', 0.1)
         self.z_translation_range = config.get('z_translation_range', 0.1)
@@ -300,8 +308,11 @@ class GAN2Shape(nn.Module):
             depth_raw, albedo, view, lighting = pre
         depth = self.get_clamped_depth(depth_raw.squeeze(1), h, w)
         view = view + self.view_light_sampler.view_mean.unsqueeze(0)
-        self._set_view(view)
         lighting = lighting + self.view_light_sampler.light_mean.unsqueeze(0)
+        flip = bool(self.flip1 if step1 else self.flip3) and not eval
+        if flip:
+            return self._step1_flipped(images, depth, albedo, view, lighting, b, kwargs.get('_defer_perc'))
+        self._set_view(view)
 
         normal = self.renderer.get_normal_from_depth(depth)
         lighting_a, lighting_b, diffuse_shading, texture = self._shade(normal, lighting, albedo)
@@ -326,6 +337,88 @@ class GAN2Shape(nn.Module):
         # loss_total = loss_l1_im + lam_perc * mean(perc) + lam_smooth * (smooth(depth) + smooth(shading))
         loss_total = weighted_total([(1.0, loss_l1_im), (self.lam_perc, self.perceptual_loss(*perc_pair))] + smooth_terms)
         return loss_total, collected
+
+    # ------------------------------------------------------------------ symmetry flips
+    def _mirror_rows(self, depth, albedo, repeat=1):
+        """(depth2, albedo2): `repeat` copies of every sample followed by `repeat` copies of its left-right mirror —
+        cat([depth.repeat_interleave(repeat, 0), depth.flip(2).repeat_interleave(repeat, 0)]) and the same of the albedo
+        with flip(3).  One kernel each way for both tensors on the GPU (fused_geometry.mirror_pair)."""
+        if depth.is_cuda and self.renderer.fused and depth.dtype == torch.float32 and albedo.dtype == torch.float32:
+            from .fused_geometry import mirror_pair
+            return mirror_pair(depth, albedo, repeat)
+
+        def rows(x):
+            return x if repeat == 1 else (x.expand(repeat, *x.shape[1:]) if x.shape[0] == 1 else x.repeat_interleave(repeat, 0))
+        return (torch.cat([rows(depth), rows(depth.flip(2))], 0), torch.cat([rows(albedo), rows(albedo.flip(3))], 0))
+
+    def _perc_terms(self, groups):
+        """LPIPS of several (weight of the group's mean, pred, target) groups through ONE trunk pass ->
+        one weighted_total term."""
+        preds, targets, weights = [], [], ()
+        for wgt, pred, target in groups:
+            n = max(len(pred), len(target))
+            preds.append(pred if len(pred) == n else pred.expand(n, *pred.shape[1:]))
+            targets.append(target if len(target) == n else target.expand(n, *target.shape[1:]))
+            weights += (wgt / n,) * n
+        return weights, self.perceptual_loss(torch.cat(preds, 0), torch.cat(targets, 0)).reshape(-1)
+
+    def _step1_flipped(self, images, depth, albedo, view, lighting, b, defer_perc):
+        """The rest of forward_step1 with the symmetry flip on: rows 0 .. B of every tensor are the plain pass, rows
+        B .. 2B the canonical depth and albedo mirrored left-right under the same view and light.
+        loss_total = l1 + lam_flip * l1_flip + lam_perc * (perc + lam_flip * perc_flip)
+                     + lam_smooth * (smooth(depth2) + smooth(diffuse_shading2));
+        `collected` holds the B plain rows only."""
+        B = len(images)
+        depth2, albedo2 = self._mirror_rows(depth, albedo)
+        view2, lighting2 = torch.cat([view, view], 0), torch.cat([lighting, lighting], 0)
+        self._set_view(view2)
+        normal2 = self.renderer.get_normal_from_depth(depth2)
+        lighting_a, lighting_b, diffuse_shading2, texture2 = self._shade(normal2, lighting2, albedo2)
+        recon_depth = self.renderer.warp_canon_depth(depth2)
+        grid_2d_from_canon = self.renderer.get_inv_warped_2d_grid(recon_depth)
+        margin = (self.max_depth - self.min_depth) / 2
+        recon_im_mask = (recon_depth < self.max_depth + margin).float().unsqueeze(1).detach()
+        recon_im = grid_sample(texture2, grid_2d_from_canon, -1, 1)
+        if B == b:      # one split (a single concatenation in backward) instead of two slices
+            (recon_b, recon_f), (mask_b, mask_f) = recon_im.split([b, b]), recon_im_mask.split([b, b])
+        else:
+            recon_b, recon_f, mask_b, mask_f = recon_im[:b], recon_im[B:B + b], recon_im_mask[:b], recon_im_mask[B:B + b]
+        terms = [(1.0, self.photometric_loss(recon_b, images, mask=mask_b)),
+                 (self.lam_flip, self.photometric_loss(recon_f, images, mask=mask_f)),
+                 (self.lam_smooth, self.smooth_loss(depth2)), (self.lam_smooth, self.smooth_loss(diffuse_shading2))]
+        perc = [(1.0, recon_b * mask_b, images * mask_b), (self.lam_flip, recon_f * mask_f, images * mask_f)]
+        canon_mask = None if B == 1 else [None] * B
+        collected = (normal2[:B], lighting_a[:B], lighting_b[:B], albedo, depth, canon_mask)
+        if defer_perc:  # the caller runs LPIPS on these groups with its own and sums the terms
+            return terms, collected, perc
+        terms.append(self._perc_terms([(self.lam_perc * wgt, p, t) for wgt, p, t in perc]))
+        return weighted_total(terms), collected
+
+    def _step3_flipped(self, step1_loss, perc1, depth, albedo, view, light, projected_samples, masks):
+        """The projected-sample half of forward_step3 with flip3 on: rows 0 .. b render the canonical depth and albedo
+        under the b predicted views and lights, rows b .. 2b their left-right mirror under the same b views and lights;
+        both halves are compared with `projected_samples`.
+        loss_total = step1_loss + l1 + lam_flip * l1_flip + lam_perc * (perc + lam_flip * perc_flip)."""
+        b = len(projected_samples)
+        depth2, albedo2 = self._mirror_rows(depth, albedo, b)
+        view2, light2, masks2 = torch.cat([view, view], 0), torch.cat([light, light], 0), torch.cat([masks, masks], 0)
+        self._set_view(view2)
+        normal2 = self.renderer.get_normal_from_depth(depth2)
+        _, _, _, texture2 = self._shade(normal2, light2, albedo2)
+        recon_depth = self.renderer.warp_canon_depth(depth2)
+        grid_2d_from_canon = self.renderer.get_inv_warped_2d_grid(recon_depth)
+        margin = (self.max_depth - self.min_depth) / 2
+        recon_im_mask = (recon_depth < self.max_depth + margin).float().unsqueeze(1).detach() * masks2
+        recon_im = grid_sample(texture2, grid_2d_from_canon, -1, 1)
+        (recon_b, recon_f), (mask_b, mask_f) = recon_im.split([b, b]), recon_im_mask.split([b, b])
+        l1 = self.photometric_loss(recon_b, projected_samples, mask=mask_b)
+        l1_flip = self.photometric_loss(recon_f, projected_samples, mask=mask_f)
+        perc = [(1.0, recon_b * mask_b, projected_samples * mask_b), (self.lam_flip, recon_f * mask_f, projected_samples * mask_f)]
+        if perc1 is not None:   # step1_loss arrives as its list of terms, its LPIPS groups join this pass's in one trunk pass
+            groups = [(self.lam_perc * wgt, p, t) for wgt, p, t in list(perc1) + perc]
+            return weighted_total(step1_loss + [(1.0, l1), (self.lam_flip, l1_flip), self._perc_terms(groups)])
+        loss_perc = sum(wgt * torch.mean(self.perceptual_loss(p, t)) for wgt, p, t in perc)
+        return step1_loss + l1 + self.lam_flip * l1_flip + self.lam_perc * loss_perc
 
     # ------------------------------------------------------------------ step 2
     def _latent_centers(self):
@@ -539,8 +632,10 @@ class GAN2Shape(nn.Module):
         normal, _, _, albedo, depth, _ = collected
 
         view = view + self.view_light_sampler.view_mean.unsqueeze(0)
-        self._set_view(view)
         light = light + self.view_light_sampler.light_mean.unsqueeze(0)
+        if self.flip3:
+            return self._step3_flipped(step1_loss, perc1, depth, albedo, view, light, projected_samples, masks), None
+        self._set_view(view)
         _, _, diffuse_shading, texture = self._shade(normal, light, albedo)
 
         depth = depth.expand(b, self.image_size, self.image_size)

@@ -110,7 +110,8 @@ class Renderer():
         if r is None:
             grid_2d = get_grid(1, h, w, normalize=False, device=device)
             grid_3d = torch.cat((grid_2d, torch.ones(1, h, w, 1, device=device)), dim=3)
-            r = grid_3d.matmul(self.inv_K.to(device).transpose(2, 1))
+            inv_K = self.inv_K.to(device)
+            r = grid_3d.to(inv_K.dtype).matmul(inv_K.transpose(2, 1))    # (a float64 check sets K / inv_K to double)
             self._rays[key] = r
         return r
 

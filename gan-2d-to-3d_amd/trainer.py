@@ -40,6 +40,10 @@ class Trainer():
         self.save_ckpts = save_ckpts
         self.debug = debug
         self.capturable = capturable  # Adam(capturable=True): needed to record steps in HIP graphs
+        # symmetry flips (model.GAN2Shape.flip1 / flip3): one bool per stage; a missing key is all False, a list
+        # shorter than the stages repeats its last entry
+        self.flip1_cfg = Trainer._flip_list(model_config.get('flip1_cfg'))
+        self.flip3_cfg = Trainer._flip_list(model_config.get('flip3_cfg'))
         prior_name = model_config.get('prior_name', 'ellipsoid')
         mask_accepts_batch = False
         if masking_model is None and model_config.get('parsing_ckpt_dir'):
@@ -70,6 +74,17 @@ class Trainer():
             self.model.load_from_checkpoint(paths[-1])
         self.history = []  # (image index, stage, step, last loss) per finished step block
 
+    @staticmethod
+    def _flip_list(value):
+        if value is None:
+            return []
+        return [bool(v) for v in value] if isinstance(value, (list, tuple)) else [bool(value)]
+
+    def _set_flips(self, stage):
+        """model.flip1 / model.flip3 of stage `stage` (flip1_cfg / flip3_cfg)."""
+        for name, cfg in (('flip1', self.flip1_cfg), ('flip3', self.flip3_cfg)):
+            setattr(self.model, name, cfg[min(stage, len(cfg) - 1)] if cfg else False)
+
     def fit(self, images_latents, plot_depth_map=False,
             stages=[{'step1': 1, 'step2': 1, 'step3': 1}] * 2, shuffle=False,
             rank=0, world_size=1, graphs=False, **_):
@@ -94,6 +109,7 @@ class Trainer():
             stage = 0
             for stage in range(n_stages):
                 old_collected = None
+                self._set_flips(stage)
                 for step in [1, 2, 3]:
                     optim = getattr(self, f'optim_step{step}')
                     forward = getattr(self.model, f'forward_step{step}')
@@ -134,10 +150,11 @@ class Trainer():
             else:
                 graphed.set_sample(image, latent)   # graphs read the static image / latent buffers
             for stage in range(len(stages)):
+                self._set_flips(stage)      # a captured step depends on its flip switch: graphs are keyed by (kind, flip)
                 for step in [1, 2, 3]:
                     n = stages[stage][f'step{step}']
                     done = 0
-                    if n > 0 and step not in graphed.graphs:
+                    if n > 0 and not graphed.captured(step):
                         if step > 1 and graphed.collected[step - 1] is None:
                             raise RuntimeError(f"step {step} needs at least one step-{step - 1} iteration first")
                         # the warm-up iterations are real iterations: never more than requested
@@ -234,6 +251,7 @@ class GeneralizingTrainer2(Trainer):
         graphed = None
         if graphs and not self.capturable:
             raise RuntimeError("graphs=True needs GeneralizingTrainer2(..., capturable=True)")
+        self._set_flips(0)      # entry 0 of flip1_cfg / flip3_cfg, as stages[0] below
         try:
             if self.load_dict is None:
                 self.model.batch_mean = whole_batch
@@ -273,7 +291,7 @@ class GeneralizingTrainer2(Trainer):
                             n3 = n3 if n2 > 0 else 0        # no step-2 hand-off, no step 3 (as in the eager loop below)
                             for step, n in ((2, n2), (3, n3)):
                                 done = 0
-                                if n > 0 and step not in graphed.graphs:     # warm-up iterations are real iterations
+                                if n > 0 and not graphed.captured(step):     # warm-up iterations are real iterations
                                     done = graphed.capture(step, warmup=min(graphed.warmup, n))
                                 for _ in range(n - done):
                                     graphed.run(step)

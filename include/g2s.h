@@ -1072,6 +1072,24 @@ int g2s_resize_u8(const uint8_t *src, uint8_t *dst, uint8_t *tmp, int N, int H, 
                   const int32_t *kx, const int32_t *bx, int ksx, const int32_t *ky, const int32_t *by, int ksy,
                   int left, int top, int ow_c, int oh_c, int row0, int rows, g2s_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Symmetry pair of a flipped step (csrc/mirror.hip; model.py forward_step1 / forward_step3 with flip1 / flip3).
+ *
+ * g2s_mirror_pair_fwd: x [N, C, H, W], repeat >= 1 -> y [2 N repeat, C, H, W]: row n * repeat + r is x[n], row
+ *   N * repeat + n * repeat + r is x[n] mirrored along W (y[.., w] = x[.., W - 1 - w]).  Two tensors that share
+ *   N, H, W and repeat (the depth, C0 = 1, and the albedo, C1 = 3) go through ONE launch; the second is optional
+ *   (x1 = y1 = NULL, C1 = 0).
+ * g2s_mirror_pair_bwd: gy [2 N repeat, C, H, W] -> gx [N, C, H, W], fully overwritten: gx[n] = sum_r gy[n * repeat + r]
+ *   + sum_r mirror(gy[N * repeat + n * repeat + r]), added in that order, r ascending.  A gather without atomics:
+ *   bit-reproducible in every mode (g2s_set_deterministic changes nothing); repeat = 1 is one f32 addition.
+ *   16-byte accesses for a tensor whose two pointers are 16-byte aligned when W % 4 == 0 (the mirror of the float4
+ *   at column quad q is the reversed float4 at quad W / 4 - 1 - q), a scalar path otherwise, chosen per tensor.
+ * ---------------------------------------------------------------------------------------- */
+int g2s_mirror_pair_fwd(const float *x0, float *y0, int C0, const float *x1, float *y1, int C1, int N, int H, int W,
+                        int repeat, g2s_stream_t stream);
+int g2s_mirror_pair_bwd(const float *gy0, float *gx0, int C0, const float *gy1, float *gx1, int C1, int N, int H,
+                        int W, int repeat, g2s_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
