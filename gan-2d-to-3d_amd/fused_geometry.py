@@ -303,6 +303,25 @@ def mirror_pair(depth, albedo=None, repeat=1):
     return MirrorPairFunction.apply(depth, albedo, repeat)
 
 
+def canon_mask(depth, rays, R, t, K9, rcd, mask):
+    """Renderer.canon_mask as one launch (csrc/canon_mask.hip): depth [B,H,W], rays [H*W,3], R [B,3,3], t [B,1,3],
+    mask [B or 1,1,H,W] -> [B,1,H,W].  No gradient: the mask is data, and nothing of the result is recorded."""
+    _lib.require_cuda(depth, rays, R, t, mask)
+    with torch.no_grad():
+        depth, R, t, mask = _f32c(depth), _f32c(R), _f32c(t), _f32c(mask)
+        B, H, W = depth.shape
+        Bm = mask.shape[0]
+        if tuple(mask.shape) != (Bm, 1, H, W) or Bm not in (1, B) or R.shape[0] != B or t.numel() != 3 * B \
+                or rays.numel() != 3 * H * W:
+            raise ValueError(f"canon_mask: depth {tuple(depth.shape)}, mask {tuple(mask.shape)}, R {tuple(R.shape)}, "
+                             f"t {tuple(t.shape)} and rays {tuple(rays.shape)} do not fit")
+        out = torch.empty((B, 1, H, W), dtype=torch.float32, device=depth.device)
+        Kc = (_lib.C.c_float * 9)(*K9)
+        _lib.check(_lib.load().g2s_canon_mask(_lib.ptr(depth), _lib.ptr(_f32c(rays)), _lib.ptr(R), _lib.ptr(t), Kc,
+                                              float(rcd), _lib.ptr(mask), _lib.ptr(out), B, Bm, H, W, _lib.stream()))
+    return out
+
+
 def depth_head(raw, W, lo, hi, clamp_border, border_depth):
     return DepthHeadFunction.apply(raw, W, lo, hi, clamp_border, border_depth)
 

@@ -14,7 +14,10 @@ otherwise autograd's AccumulateGrad nodes stay bound to the legacy default strea
 aborts.
 
 Static buffers: `image`, `latent` (copy a new image in to reuse the graphs), and the `collected`
-hand-offs — graph k+1 reads the output tensors of graph k in place.
+hand-offs — graph k+1 reads the output tensors of graph k in place.  With the object masks live
+(model.GAN2Shape.object_mask; fixed for a trainer's lifetime, so the graph keys do not carry it) a third static
+buffer holds the image's object mask: the trainer computes the mask eagerly, outside any capture, and set_sample
+copies it in; the captured step 1 (and the inner step-1 pass of step 3) turns it into the canonical mask in place.
 
 Symmetry flips: a captured step 1 / step 3 depends on the model's flip switch (flip1 / flip3: twice the rows
 behind the nets), so the graphs are keyed by (kind, flip) and a schedule whose stages differ captures each variant
@@ -27,11 +30,12 @@ from . import zeropool
 
 
 class GraphedSteps:
-    def __init__(self, trainer, image, latent, warmup=3):
+    def __init__(self, trainer, image, latent, warmup=3, object_mask=None):
         self.t = trainer
         self.model = trainer.model
         self.image = image.clone()
         self.latent = latent.clone()
+        self.object_mask = None if object_mask is None else object_mask.detach().clone()
         self.graphs = {}
         self.loss = {}
         self.collected = {1: None, 2: None, 3: None}
@@ -44,10 +48,15 @@ class GraphedSteps:
                     raise RuntimeError("GraphedSteps needs Adam(capturable=True): build the trainer "
                                        "with Trainer(..., capturable=True)")
 
+    def _step_kwargs(self):
+        kw = {'n_proj_samples': self.t.n_proj_samples}
+        if self.object_mask is not None:
+            kw['object_mask'] = self.object_mask
+        return kw
+
     def _iteration(self, kind, src):
         optim = getattr(self.t, f'optim_step{kind}')
-        loss, collected = getattr(self.model, f'forward_step{kind}')(
-            self.image, self.latent, src, n_proj_samples=self.t.n_proj_samples)
+        loss, collected = getattr(self.model, f'forward_step{kind}')(self.image, self.latent, src, **self._step_kwargs())
         loss.backward()
         optim.step()
         zeropool.end()
@@ -130,9 +139,14 @@ class GraphedSteps:
         self._publish(kind, *self._outputs[key])
         return self.loss[kind]
 
-    def set_sample(self, image, latent):
+    def set_sample(self, image, latent, object_mask=None):
         self.image.copy_(image)
         self.latent.copy_(latent)
+        if (object_mask is None) != (self.object_mask is None):
+            raise ValueError("the object mask is a static buffer of the captured graphs: give one with every sample, or "
+                             "with none")
+        if object_mask is not None:
+            self.object_mask.copy_(object_mask)
 
 
 class GraphedJointSteps(GraphedSteps):
@@ -149,15 +163,14 @@ class GraphedJointSteps(GraphedSteps):
     single process, or one image per rank WITHOUT the whole-batch centre) and is refused otherwise — the
     trainer then runs it eagerly (sharding.global_mean is a differentiable all-reduce inside the forward)."""
 
-    def __init__(self, trainer, image, latent, warmup=3):
-        super().__init__(trainer, image, latent, warmup)
+    def __init__(self, trainer, image, latent, warmup=3, object_mask=None):
+        super().__init__(trainer, image, latent, warmup, object_mask)
         from .sharding import bucket_of
         self.buckets = {k: bucket_of([p for g in getattr(trainer, f'optim_step{k}').param_groups for p in g['params']])
                         for k in (1, 2, 3)}
 
     def _forward_backward(self, kind, src):
-        loss, collected = getattr(self.model, f'forward_step{kind}')(
-            self.image, self.latent, src, n_proj_samples=self.t.n_proj_samples)
+        loss, collected = getattr(self.model, f'forward_step{kind}')(self.image, self.latent, src, **self._step_kwargs())
         loss.backward()
         self.buckets[kind].pack()
         return loss, collected

@@ -149,6 +149,7 @@ SIGNATURES = {
     "g2s_resize_u8": (_i, [_p, _p, _p] + [_i] * 5 + [_p, _p, _i, _p, _p, _i] + [_i] * 6 + [_p]),
     "g2s_mirror_pair_fwd": (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p]),
     "g2s_mirror_pair_bwd": (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "g2s_canon_mask": (_i, [_p, _p, _p, _p, _p, _f, _p, _p, _i, _i, _i, _i, _p]),
 }
 
 

@@ -71,6 +71,13 @@ class GAN2Shape(nn.Module):
     flip1 = False
     flip3 = False
     lam_flip = 0.5
+    # the object mask inside the steps (added; the reference reads `use_mask` and leaves `FIXME include use_mask bool?`
+    # where the canonical mask would be made, model.py:165-172): config `object_mask` (default False) AND `use_mask`
+    # make the masks live — step 1 then carries the input image's object mask into the canonical frame
+    # (Renderer.canon_mask) and hands it on in the last slot of `collected`.  `use_mask` alone switches nothing on: it
+    # is True in every existing config.
+    object_mask = False
+    use_mask = True
 
     def __init__(self, config, debug=False, device="cuda"):
         super().__init__()
@@ -135,6 +142,7 @@ class GAN2Shape(nn.Module):
         self.xy_translation_range = config.get('xy_translation_range', 0.1)
         self.z_translation_range = config.get('z_translation_range', 0.1)
         self.use_mask = config.get('use_mask', True)
+        self.object_mask = bool(config.get('object_mask', False))
         self.relative_encoding = config.get('relative_encoding', False)
         self.rand_light = config.get('rand_light', [-1, 1, -0.2, 0.8, -0.1, 0.6, -0.6])
         self.truncation = config.get('truncation', 1)
@@ -238,6 +246,11 @@ class GAN2Shape(nn.Module):
         diffuse_shading, texture = self.get_shading(normal, lighting_a, lighting_b, lighting_d, albedo)
         return lighting_a, lighting_b, diffuse_shading, texture
 
+    @property
+    def masks_live(self):
+        """True when step 1 makes a canonical object mask: config `object_mask` and `use_mask` both on."""
+        return bool(self.object_mask) and bool(self.use_mask)
+
     @staticmethod
     def _head(x, n):
         """x[:n]; the tensor itself when it has exactly n rows (an identity slice would still cost a
@@ -272,13 +285,22 @@ class GAN2Shape(nn.Module):
         return outs
 
     # ------------------------------------------------------------------ step 1
-    def forward_step1(self, images, latents, collected, step1=True, eval=False, **kwargs):
+    def forward_step1(self, images, latents, collected, step1=True, eval=False, object_mask=None, **kwargs):
         """model.py:95-173: optimise the albedo net (step1=True) / everything (step1=False).
+
+        object_mask: the object mask of `images`, (B,1,S,S) or (1,1,S,S) float in [0, 1]; required when the masks are
+        live (`masks_live`), ignored otherwise.  The canonical mask made from it (Renderer.canon_mask of the
+        unflipped canonical depth under the step's view) goes into the last slot of `collected`; the step's own
+        loss terms do not read it.
 
         `_nets`, `_defer_perc` are internal (forward_step3 batches the image with its projected
         samples through V / L and through LPIPS; the arithmetic per sample is unchanged)."""
         b = 1
         h, w = self.image_size, self.image_size
+        live = self.masks_live and not eval
+        if live and object_mask is None:
+            raise ValueError("object_mask is on (config object_mask and use_mask): forward_step1 / forward_step3 need "
+                             "object_mask=, the object mask of the image (B,1,S,S)")
         if eval:
             zeropool.end()      # evaluation is no training step: nothing of it is served from (or left in) a step's pool
         elif step1 and images.is_cuda:   # a step of its own (forward_step3 begins the pool for its inner call)
@@ -310,9 +332,16 @@ class GAN2Shape(nn.Module):
         view = view + self.view_light_sampler.view_mean.unsqueeze(0)
         lighting = lighting + self.view_light_sampler.light_mean.unsqueeze(0)
         flip = bool(self.flip1 if step1 else self.flip3) and not eval
+        canon_mask = None if len(images) == 1 else [None] * len(images)
+        if live:    # from the unflipped canonical depth under the step's view, whichever branch follows
+            self._set_view(view)
+            canon_mask = self.renderer.canon_mask(depth, object_mask)
+            if len(images) > 1:
+                canon_mask = list(canon_mask.split(1))
         if flip:
-            return self._step1_flipped(images, depth, albedo, view, lighting, b, kwargs.get('_defer_perc'))
-        self._set_view(view)
+            return self._step1_flipped(images, depth, albedo, view, lighting, b, kwargs.get('_defer_perc'), canon_mask)
+        if not live:
+            self._set_view(view)
 
         normal = self.renderer.get_normal_from_depth(depth)
         lighting_a, lighting_b, diffuse_shading, texture = self._shade(normal, lighting, albedo)
@@ -330,7 +359,6 @@ class GAN2Shape(nn.Module):
         loss_l1_im = self.photometric_loss(recon_b, images, mask=mask_b)
         perc_pair = (recon_b * mask_b, images * mask_b)
         smooth_terms = [(self.lam_smooth, self.smooth_loss(depth)), (self.lam_smooth, self.smooth_loss(diffuse_shading))]
-        canon_mask = None if len(images) == 1 else [None] * len(images)
         collected = (normal, lighting_a, lighting_b, albedo, depth, canon_mask)
         if kwargs.get('_defer_perc'):  # caller adds lam_perc * mean(LPIPS(*perc_pair)) and sums the terms
             return [(1.0, loss_l1_im)] + smooth_terms, collected, perc_pair
@@ -362,12 +390,13 @@ class GAN2Shape(nn.Module):
             weights += (wgt / n,) * n
         return weights, self.perceptual_loss(torch.cat(preds, 0), torch.cat(targets, 0)).reshape(-1)
 
-    def _step1_flipped(self, images, depth, albedo, view, lighting, b, defer_perc):
+    def _step1_flipped(self, images, depth, albedo, view, lighting, b, defer_perc, canon_mask=None):
         """The rest of forward_step1 with the symmetry flip on: rows 0 .. B of every tensor are the plain pass, rows
         B .. 2B the canonical depth and albedo mirrored left-right under the same view and light.
         loss_total = l1 + lam_flip * l1_flip + lam_perc * (perc + lam_flip * perc_flip)
                      + lam_smooth * (smooth(depth2) + smooth(diffuse_shading2));
-        `collected` holds the B plain rows only."""
+        `collected` holds the B plain rows only; `canon_mask` (its last slot) is handed through as forward_step1 made
+        it from the unflipped depth."""
         B = len(images)
         depth2, albedo2 = self._mirror_rows(depth, albedo)
         view2, lighting2 = torch.cat([view, view], 0), torch.cat([lighting, lighting], 0)
@@ -387,7 +416,6 @@ class GAN2Shape(nn.Module):
                  (self.lam_flip, self.photometric_loss(recon_f, images, mask=mask_f)),
                  (self.lam_smooth, self.smooth_loss(depth2)), (self.lam_smooth, self.smooth_loss(diffuse_shading2))]
         perc = [(1.0, recon_b * mask_b, images * mask_b), (self.lam_flip, recon_f * mask_f, images * mask_f)]
-        canon_mask = None if B == 1 else [None] * B
         collected = (normal2[:B], lighting_a[:B], lighting_b[:B], albedo, depth, canon_mask)
         if defer_perc:  # the caller runs LPIPS on these groups with its own and sums the terms
             return terms, collected, perc
@@ -531,14 +559,17 @@ class GAN2Shape(nn.Module):
         return pseudo_im.clamp(min=-1, max=1), mask.contiguous()
 
     # ------------------------------------------------------------------ manipulation through the GAN
-    def decompose(self, image):
+    def decompose(self, image, object_mask=None):
         """The head of forward_step1 without its losses, under no_grad: the four nets on `image` (1,3,S,S) ->
         dict(collected=(normal, light_a, light_b, albedo, depth, canon_mask) as forward_step1 returns it, view (1,6)
         and light (1,4): the predicted view and lighting with the sampler's means added, as the nets give them).
         forward_step1 itself is not called: it would run the losses and begin a training step's pool, and it does
         not hand out the raw view and lighting.  This is therefore a second statement of its head (each net called
         on its own, not through the paired or forked routes, which differ in rounding only) and HAS TO FOLLOW any
-        change made there; tests/test_gpu_manipulate.py holds the two to each other."""
+        change made there; tests/test_gpu_manipulate.py holds the two to each other.
+        object_mask (1,1,S,S), optional: the object mask of `image`; when given, canon_mask is Renderer.canon_mask of
+        the canonical depth under the predicted view, as forward_step1 makes it with the masks live (an explicit
+        request here: the config switch governs the training steps)."""
         with torch.no_grad():
             h = w = self.image_size
             depth = self.get_clamped_depth(self.depth_net(image).squeeze(1), h, w)
@@ -547,9 +578,13 @@ class GAN2Shape(nn.Module):
             light = self.lighting_net(image) + self.view_light_sampler.light_mean.unsqueeze(0)
             normal = self.renderer.get_normal_from_depth(depth)
             ab = light[:, :2] / 2 + 0.5
-        return dict(collected=(normal, ab[:, :1], ab[:, 1:2], albedo, depth, None), view=view, light=light)
+            canon_mask = None
+            if object_mask is not None:
+                self._set_view(view)
+                canon_mask = self.renderer.canon_mask(depth, object_mask)
+        return dict(collected=(normal, ab[:, :1], ab[:, 1:2], albedo, depth, canon_mask), view=view, light=light)
 
-    def manipulate(self, image, latent, views, lights=None, relative=False, gan_batch=8):
+    def manipulate(self, image, latent, views, lights=None, relative=False, gan_batch=8, object_mask=None):
         """3D-aware manipulation through the GAN: the recovered shape of `image` (1,3,S,S) rotated and relit, every
         frame pushed through the offset encoder and the frozen generator, as the forward half of step 2 does for
         its random draws.  latent: the image's w (style_dim,) or (1,style_dim).  views (V,6): one pose per frame in
@@ -557,6 +592,8 @@ class GAN2Shape(nn.Module):
         canonical frame, or composed after the predicted view when `relative` (zeros = the input's own pose).
         lights (V,4): raw (a, b, dx, dy) rows as the lighting net gives them (`light_sweep`), None = the predicted
         light on every frame.  The generator runs `gan_batch` frames at a time with its fixed noise buffers.
+        object_mask (1,1,S,S), optional: the object mask of `image`; its canonical form (`decompose`) is warped with
+        every frame and comes back as `mask`.
         Under no_grad.  Returns dict(pseudo (V,3,S,S) the rendered frames, mask (V,1,S,S), gan (V,3,S,S) the GAN's
         images resized to image_size, w (V,style_dim) = latent + offset, view (1,6), light (1,4) the predictions)."""
         F1_d = 2
@@ -571,7 +608,7 @@ class GAN2Shape(nn.Module):
             if views.dim() != 2 or views.shape[1] != 6:
                 raise ValueError(f"views must be (V, 6), got {tuple(views.shape)}")
             V = views.shape[0]
-            d = self.decompose(image)
+            d = self.decompose(image, object_mask)
             normal, _, _, albedo, depth, canon_mask = d["collected"]
             if lights is None:
                 lights = d["light"].expand(V, 4)
@@ -594,9 +631,14 @@ class GAN2Shape(nn.Module):
         return dict(pseudo=pseudo, mask=mask, gan=torch.cat(frames, 0), w=w, view=d["view"], light=d["light"])
 
     # ------------------------------------------------------------------ step 3
-    def forward_step3(self, images, latents, collected, **kwargs):
-        """model.py:225-280: optimise V, L, D, A on the image and its projected samples."""
+    def forward_step3(self, images, latents, collected, object_mask=None, **kwargs):
+        """model.py:225-280: optimise V, L, D, A on the image and its projected samples.  object_mask: as in
+        forward_step1, for the inner step-1 pass; step 2's `masks` (which carry the warped canonical mask) multiply
+        into the reconstruction mask as they always did."""
         projected_samples, masks = collected
+        if self.masks_live and object_mask is None:      # before any work: the inner step-1 pass would refuse it
+            raise ValueError("object_mask is on (config object_mask and use_mask): forward_step3 needs object_mask=, the "
+                             "object mask of the image (B,1,S,S)")
         if images.is_cuda:
             zeropool.begin(3, images.device)
         # the reference draws (and discards) a permutation here (model.py:231-233): keep the draw so
@@ -624,9 +666,9 @@ class GAN2Shape(nn.Module):
             light1, light = light_all.split([1, b])
             step1_loss, collected, perc1 = self.forward_step1(
                 images, None, None, step1=False, _nets=(depth_raw, albedo1, view1, light1),
-                _defer_perc=True)
+                _defer_perc=True, object_mask=object_mask)
         else:
-            step1_loss, collected = self.forward_step1(images, None, None, step1=False)
+            step1_loss, collected = self.forward_step1(images, None, None, step1=False, object_mask=object_mask)
             perc1 = None
             view, light = self.viewpoint_net(projected_samples), self.lighting_net(projected_samples)
         normal, _, _, albedo, depth, _ = collected

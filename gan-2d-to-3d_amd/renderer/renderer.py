@@ -148,6 +148,27 @@ class Renderer():
     def get_warped_2d_grid(self, depth):
         return self.grid_3d_to_2d(self.get_warped_3d_grid(depth))
 
+    def canon_mask(self, depth, mask):
+        """The object mask of the input image carried into the canonical frame (added; the reference leaves the
+        place open, model.py:165-172): every canonical pixel reads `mask` where the view set by set_view /
+        set_transform_matrices puts it in the input image,
+            grid_sample(mask, get_warped_2d_grid(depth), bilinear, zeros padding, align_corners=True).detach().
+        depth (B,S,S) canonical; mask (B,1,S,S) or (1,1,S,S) (shared by the batch), float in [0, 1] -> (B,1,S,S), no
+        gradient.  One launch on the GPU (g2s_canon_mask, csrc/canon_mask.hip); the torch composition below is its
+        specification and the route of CPU and float64 tensors."""
+        b, h, w = depth.shape
+        if mask.dim() != 4 or mask.shape[1] != 1 or mask.shape[0] not in (1, b) or tuple(mask.shape[2:]) != (h, w):
+            raise ValueError(f"canon_mask: mask must be ({b},1,{h},{w}) or (1,1,{h},{w}), got {tuple(mask.shape)}")
+        mask = mask.detach().to(device=depth.device, dtype=depth.dtype)
+        if self._use_fused(depth):
+            rays = self._pixel_rays(h, w, depth.device).reshape(-1, 3)
+            return fg.canon_mask(depth.detach(), rays, self.rot_mat, self.trans_xyz, self._K9,
+                                 self.rot_center_depth, mask)
+        with torch.no_grad():
+            grid = self.get_warped_2d_grid(depth)
+            return nn.functional.grid_sample(mask.expand(b, 1, h, w), grid, mode='bilinear', padding_mode='zeros',
+                                             align_corners=True)
+
     def get_inv_warped_2d_grid(self, depth):
         if self._use_fused(depth):
             b, h, w = depth.shape

@@ -13,6 +13,7 @@ are carried from image to image, so a shard equals the reference run on that ran
 Plotting / wandb hooks are out of scope.
 """
 import logging
+import os
 
 import torch
 from torch.utils.data import DataLoader, Subset
@@ -21,11 +22,26 @@ from . import zeropool
 from .priors import PriorGenerator
 from .sharding import shard_indices  # noqa: F401  (re-exported)
 
+_NO_MASK_SOURCE = ("object_mask is on but there is no source of object masks: set `parsing_ckpt_dir` to the directory of "
+                   "the parsing checkpoints, or pass object_mask_fn= (or masking_model=) to the trainer")
+
+
+def object_masks_live(config):
+    """Whether the steps carry an object mask: config `object_mask` (default False) AND `use_mask` (default True), as
+    model.GAN2Shape.masks_live."""
+    return bool(config.get('object_mask', False)) and bool(config.get('use_mask', True))
+
 
 class Trainer():
     def __init__(self, model, model_config, debug=False, plot_intermediate=False, log_wandb=False,
                  save_ckpts=False, load_dict=None, masking_model=None, device="cuda",
-                 capturable=False):
+                 capturable=False, object_mask_fn=None):
+        # object masks inside the steps (model.GAN2Shape.object_mask): live when config `object_mask` and `use_mask`
+        # are both on; fixed for the trainer's lifetime.  Without a source of masks nothing is built.
+        self.object_mask = object_masks_live(model_config)
+        ckpt_dir = model_config.get('parsing_ckpt_dir')
+        if self.object_mask and object_mask_fn is None and masking_model is None and not (ckpt_dir and os.path.isdir(ckpt_dir)):
+            raise ValueError(_NO_MASK_SOURCE)
         try:
             self.model = model(model_config, debug, device=device)
         except TypeError:  # a model class with the reference's exact (config, debug) signature
@@ -46,14 +62,27 @@ class Trainer():
         self.flip3_cfg = Trainer._flip_list(model_config.get('flip3_cfg'))
         prior_name = model_config.get('prior_name', 'ellipsoid')
         mask_accepts_batch = False
-        if masking_model is None and model_config.get('parsing_ckpt_dir'):
+        want_parser_mask = self.object_mask and object_mask_fn is None
+        parser = None
+        if (masking_model is None or want_parser_mask) and model_config.get('parsing_ckpt_dir'):
             # config `parsing_ckpt_dir` names an existing directory: the parsing net of the category (parsing.py)
             # supplies the masks, batched; otherwise the synthetic mask stays
             from .parsing import masking_model_from_config
             parser = masking_model_from_config(model_config, device=self.device)
-            if parser is not None:
-                masking_model = parser.confidence_mask if 'confidence' in prior_name else parser.image_mask
-                mask_accepts_batch = True
+        # the source of the object masks: the argument, else the parsing net's image_mask, else `masking_model`
+        self.object_mask_fn, self._object_mask_batched = None, True
+        if self.object_mask:
+            if object_mask_fn is not None:
+                self.object_mask_fn = object_mask_fn
+            elif parser is not None:
+                self.object_mask_fn = parser.image_mask
+            elif masking_model is not None:
+                self.object_mask_fn, self._object_mask_batched = masking_model, False    # one image per call
+            else:
+                raise ValueError(_NO_MASK_SOURCE)
+        if masking_model is None and parser is not None:
+            masking_model = parser.confidence_mask if 'confidence' in prior_name else parser.image_mask
+            mask_accepts_batch = True
         self.prior_generator = PriorGenerator(self.image_size, self.category, prior_name,
                                               masking_model=masking_model,
                                               on_device=model_config.get('prior_on_device', False),
@@ -79,6 +108,26 @@ class Trainer():
         if value is None:
             return []
         return [bool(v) for v in value] if isinstance(value, (list, tuple)) else [bool(value)]
+
+    def object_masks(self, images):
+        """The object masks of `images` (B,3,S,S) from the trainer's source -> (B,1,S,S) float32 on the device, no
+        gradient; None when the masks are off.  Computed eagerly, once per image (fit) or per batch (the joint loop)."""
+        if not self.object_mask:
+            return None
+        with torch.no_grad():
+            fn = self.object_mask_fn
+            if self._object_mask_batched or len(images) == 1:
+                masks = torch.as_tensor(fn(images))
+            else:
+                masks = torch.cat([torch.as_tensor(fn(images[i:i + 1])).reshape(1, 1, *images.shape[-2:])
+                                   for i in range(len(images))], 0)
+            masks = masks.to(device=self.device, dtype=torch.float32).reshape(len(images), 1, *images.shape[-2:])
+        return masks.detach().contiguous()
+
+    def _mask_kwargs(self, masks):
+        """The extra keyword of a step call: object_mask= when the masks are live, nothing otherwise (a model class
+        with the reference's exact step signatures sees the call it always saw)."""
+        return {} if masks is None else {'object_mask': masks}
 
     def _set_flips(self, stage):
         """model.flip1 / model.flip3 of stage `stage` (flip1_cfg / flip3_cfg)."""
@@ -106,6 +155,7 @@ class Trainer():
             logging.info(f'Training on image {data_index}')
             if not self.debug and self.load_dict is None:
                 self.pretrain_on_prior(image, data_index, plot_depth_map)
+            mask_kw = self._mask_kwargs(self.object_masks(image))       # once per image
             stage = 0
             for stage in range(n_stages):
                 old_collected = None
@@ -117,7 +167,7 @@ class Trainer():
                     for _ in range(stages[stage][f'step{step}']):
                         optim.zero_grad()
                         loss, collected = forward(image, latent, old_collected,
-                                                  n_proj_samples=self.n_proj_samples)
+                                                  n_proj_samples=self.n_proj_samples, **mask_kw)
                         loss.backward()
                         optim.step()
                         zeropool.end()       # the step's cleared pool serves nothing beyond the step
@@ -145,10 +195,11 @@ class Trainer():
             data_index = int(data_index[0])
             if not self.debug and self.load_dict is None:
                 self.pretrain_on_prior(image, data_index)
+            masks = self.object_masks(image)    # eagerly, outside any capture
             if graphed is None:
-                graphed = GraphedSteps(self, image, latent)
+                graphed = GraphedSteps(self, image, latent, object_mask=masks)
             else:
-                graphed.set_sample(image, latent)   # graphs read the static image / latent buffers
+                graphed.set_sample(image, latent, masks)   # graphs read the static image / latent / mask buffers
             for stage in range(len(stages)):
                 self._set_flips(stage)      # a captured step depends on its flip switch: graphs are keyed by (kind, flip)
                 for step in [1, 2, 3]:
@@ -261,9 +312,10 @@ class GeneralizingTrainer2(Trainer):
                                                                     rank, world_size):
                     loss = collected = None
                     self.model.batch_mean = whole_batch
+                    masks = self.object_masks(images)       # once per batch
                     for _ in range(stages[0]['step1']):
                         self.optim_step1.zero_grad()
-                        loss, collected = self.model.forward_step1(images, latents, None)
+                        loss, collected = self.model.forward_step1(images, latents, None, **self._mask_kwargs(masks))
                         loss.backward()
                         self._sync_and_step(self.optim_step1)
                         total_it += 1
@@ -276,6 +328,7 @@ class GeneralizingTrainer2(Trainer):
                         canon_masks = [canon_masks]
                     for bi, index in enumerate(indices):
                         image, latent = images[bi:bi + 1], latents[bi:bi + 1]
+                        mask_kw = self._mask_kwargs(None if masks is None else masks[bi:bi + 1])    # this sample's mask
                         step1_collected = (normals[bi:bi + 1].detach(), lights_a[bi:bi + 1].detach(),
                                            lights_b[bi:bi + 1].detach(), albedos[bi:bi + 1].detach(),
                                            depths[bi:bi + 1].detach(), canon_masks[bi])
@@ -283,9 +336,9 @@ class GeneralizingTrainer2(Trainer):
                         if graphs:
                             from .graphs import GraphedJointSteps
                             if graphed is None:
-                                graphed = GraphedJointSteps(self, image, latent)
+                                graphed = GraphedJointSteps(self, image, latent, object_mask=mask_kw.get('object_mask'))
                             else:
-                                graphed.set_sample(image, latent)
+                                graphed.set_sample(image, latent, mask_kw.get('object_mask'))
                             graphed.set_source(2, step1_collected)
                             n2, n3 = stages[0]['step2'], stages[0]['step3']
                             n3 = n3 if n2 > 0 else 0        # no step-2 hand-off, no step 3 (as in the eager loop below)
@@ -304,13 +357,13 @@ class GeneralizingTrainer2(Trainer):
                         for _ in range(stages[0]['step2']):
                             self.optim_step2.zero_grad()
                             loss2, step2_collected = self.model.forward_step2(
-                                image, latent, step1_collected, n_proj_samples=self.n_proj_samples)
+                                image, latent, step1_collected, n_proj_samples=self.n_proj_samples, **mask_kw)
                             loss2.backward()
                             self._sync_and_step(self.optim_step2)
                             total_it += 1
                         for _ in range(stages[0]['step3'] if step2_collected is not None else 0):
                             self.optim_step3.zero_grad()
-                            loss3, _c = self.model.forward_step3(image, latent, step2_collected)
+                            loss3, _c = self.model.forward_step3(image, latent, step2_collected, **mask_kw)
                             loss3.backward()
                             self._sync_and_step(self.optim_step3)
                             total_it += 1

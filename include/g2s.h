@@ -1090,6 +1090,22 @@ int g2s_mirror_pair_fwd(const float *x0, float *y0, int C0, const float *x1, flo
 int g2s_mirror_pair_bwd(const float *gy0, float *gx0, int C0, const float *gy1, float *gx1, int C1, int N, int H,
                         int W, int repeat, g2s_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Canonical object mask (csrc/canon_mask.hip; Renderer.canon_mask, model.py forward_step1 with object_mask on).
+ *
+ * g2s_canon_mask: out [B, 1, H, W] = grid_sample(mask, get_warped_2d_grid(depth), bilinear, zeros padding,
+ *   align_corners=True) in ONE launch: per canonical pixel p of sample b
+ *     Y = R_b (d ray_p - c) + c + t_b,   (u, v) = K (Y / Y.z),   g = (u / (W - 1), v / (H - 1)) * 2 - 1
+ *   and the four-tap bilinear read of the mask at g, taps outside the image counting as 0.
+ *   depth [B, H, W], rays [H*W, 3], R [B,3,3], t [B,3], K a HOST pointer to 9 floats, rot_center_depth = c.z as for
+ *   g2s_warp_verts_fwd; mask [Bm, 1, H, W] with Bm = B, or Bm = 1 (one mask shared by the batch).  All f32.
+ *   No gradient, no workspace, no atomics: every element is written once from the inputs alone, bit-identical from run
+ *   to run in every mode.  A pixel whose position is not finite reads nothing and gives 0.
+ * ---------------------------------------------------------------------------------------- */
+int g2s_canon_mask(const float *depth, const float *rays, const float *R, const float *t, const float *K,
+                   float rot_center_depth, const float *mask, float *out, int B, int Bm, int H, int W,
+                   g2s_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
