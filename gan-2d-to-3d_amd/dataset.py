@@ -15,17 +15,33 @@ from PIL import Image
 from torch.utils.data import Dataset
 
 
-def default_transform(image_size):
+def default_transform(image_size, crop=None, origin_size=None):
     """PIL image -> float tensor (3,H,W) in [0,1]; the smaller edge is resized to `image_size`
-    (bilinear), as torchvision's Resize(int) + ToTensor do."""
+    (bilinear), as torchvision's Resize(int) + ToTensor do.
+    With `crop` (config keys `crop` / `origin_size`, the framing of GAN2Shape/model.py:197-200 applied to the input
+    image): the smaller edge goes to `origin_size` (default `image_size`), the centre crop x crop window is cut
+    (margin (edge - crop) // 2 per axis, as utils.crop) and resized to image_size x image_size (bilinear)."""
+    if crop is None:
+        edge = image_size
+    else:
+        edge = image_size if origin_size is None else int(origin_size)
+        crop = int(crop)
+        if not 0 < crop <= edge:
+            raise ValueError(f"crop must satisfy 0 < crop <= origin_size, got crop {crop}, origin_size {edge}")
+
     def transform(image):
         w, h = image.size
         if w <= h:
-            size = (image_size, max(1, int(image_size * h / w)))
+            size = (edge, max(1, int(edge * h / w)))
         else:
-            size = (max(1, int(image_size * w / h)), image_size)
+            size = (max(1, int(edge * w / h)), edge)
         if (w, h) != size:
             image = image.resize(size, Image.BILINEAR)
+        if crop is not None:
+            left, top = (size[0] - crop) // 2, (size[1] - crop) // 2
+            image = image.crop((left, top, left + crop, top + crop))
+            if crop != image_size:
+                image = image.resize((image_size, image_size), Image.BILINEAR)
         a = np.asarray(image.convert('RGB'), dtype=np.uint8)
         return torch.from_numpy(a.copy()).permute(2, 0, 1).float().div(255)
     return transform

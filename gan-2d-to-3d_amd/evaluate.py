@@ -148,7 +148,7 @@ def main(argv=None, model=None, masking_model=None):
         masking_model = MaskingModel(category, device=device, ckpt_dir=config["parsing_ckpt_dir"],
                                      size=config.get("parsing_size"))
     dataset = ImageDataset(os.path.join(config["root_path"], category), subset=args.images,
-                           transform=default_transform(config["image_size"]))
+                           transform=default_transform(config["image_size"], config.get("crop"), config.get("origin_size")))
     return evaluate(model, dataset, args.out, masking_model=masking_model if args.mask else None,
                     gt_depth_dir=args.gt_depth, gt_background=args.gt_background, record_loss=args.record_loss, device=device)
 

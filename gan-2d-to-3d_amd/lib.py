@@ -150,6 +150,10 @@ SIGNATURES = {
     "g2s_mirror_pair_fwd": (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p]),
     "g2s_mirror_pair_bwd": (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p]),
     "g2s_canon_mask": (_i, [_p, _p, _p, _p, _p, _f, _p, _p, _i, _i, _i, _i, _p]),
+    "g2s_resample_max_taps": (_i, []),
+    "g2s_resample_tile_rows": (_i, [_i] * 6),
+    "g2s_resample_bands_check": (_i, [_p, _p, _i, _i, _i]),
+    "g2s_resample_sep": (_i, [_p, _p] + [_i] * 5 + [_p, _p, _p, _i, _p, _p, _p, _i, _p]),
 }
 
 

@@ -78,7 +78,8 @@ def main(argv=None, model=None):
         model = GAN2Shape(config, device=device)
         model.load_from_checkpoint(checkpoint_path_of(args.ckpt))
     dataset = ImageLatentDataset(os.path.join(config["root_path"], config.get("category")), subset=args.images,
-                                 transform=default_transform(config["image_size"]))
+                                 transform=default_transform(config["image_size"], config.get("crop"),
+                                                             config.get("origin_size")))
     written = []
     for i, stem in enumerate(_stems(dataset.image_dataset)):
         image, latent, _ = dataset[i]

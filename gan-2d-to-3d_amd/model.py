@@ -144,6 +144,19 @@ class GAN2Shape(nn.Module):
         self.use_mask = config.get('use_mask', True)
         self.object_mask = bool(config.get('object_mask', False))
         self.relative_encoding = config.get('relative_encoding', False)
+        # `crop` (absent = off) / `origin_size` (default image_size, read only with crop): the centre crop of step 2
+        # (model.py:197-200, 211-214, `# FIXME: add back cropping`): G's image is resized to origin_size, cropped to
+        # crop x crop and resized to image_size.  The band tables of the fused route are made (and uploaded) here,
+        # ahead of any graph capture.
+        self.crop = config.get('crop')
+        self.origin_size = None
+        self.crop_fused = None      # None: the renderer's `fused` selects the crop's route; True / False: this does
+        if self.crop is not None:
+            from .op import resample
+            self.crop = int(self.crop)
+            origin = config.get('origin_size')
+            self.origin_size = self.image_size if origin is None else int(origin)
+            resample.crop_resize_tables(config.get('gan_size'), self.origin_size, self.crop, self.image_size, self.device)
         self.rand_light = config.get('rand_light', [-1, 1, -0.2, 0.8, -0.1, 0.6, -0.6])
         self.truncation = config.get('truncation', 1)
         if self.truncation < 1:
@@ -191,6 +204,15 @@ class GAN2Shape(nn.Module):
         depth = depth.tanh()
         depth = self.rescale_depth(depth)
         return F.mse_loss(depth[0], prior.detach().expand(depth.size(1), -1, -1)), depth
+
+    def gan_to_image_size(self, gan_im):
+        """G's image in the frame of the shape: utils.resize to image_size, or with `crop` the resize -> centre crop
+        -> resize of model.py:197-200 (one launch each way when the renderer's fused route is on)."""
+        if self.crop is None:
+            return utils.resize(gan_im, [self.image_size, self.image_size])
+        from .op.resample import crop_resize
+        fused = self.renderer.fused if self.crop_fused is None else self.crop_fused
+        return crop_resize(gan_im, self.origin_size, self.crop, self.image_size, fused=fused)
 
     def get_view_transformation(self, view):
         return torch.cat([view[:, :3] * math.pi / 180 * self.xyz_rotation_range,
@@ -474,13 +496,13 @@ class GAN2Shape(nn.Module):
                 gan_im, _ = self.generator([latent], input_is_w=True,
                                            truncation_latent=self.mean_latent,
                                            truncation=self.truncation, randomize_noise=False)
-                gan_im = utils.resize(gan_im.clamp(min=-1, max=1), [self.image_size, self.image_size])
+                gan_im = self.gan_to_image_size(gan_im.clamp(min=-1, max=1))
             center_w, center_h = self._latent_centers()
 
         latent_projection = self.latent_projection(pseudo_im, gan_im, latent, center_w, center_h, F1_d)
         projected_image, offset = self.generator.invert(pseudo_im, latent_projection,
                                                         self.truncation, self.mean_latent)
-        projected_image = utils.resize(projected_image, [self.image_size, self.image_size])
+        projected_image = self.gan_to_image_size(projected_image)
         self.loss_l1 = self.photometric_loss(projected_image, pseudo_im, mask=mask)
         self.loss_rec = self.discriminator_loss(self.discriminator, projected_image, pseudo_im,
                                                 mask=mask)
@@ -620,14 +642,14 @@ class GAN2Shape(nn.Module):
             if self.relative_encoding:
                 gan_im, _ = self.generator([latent], input_is_w=True, truncation_latent=self.mean_latent,
                                            truncation=self.truncation, randomize_noise=False)
-                gan_im = utils.resize(gan_im.clamp(min=-1, max=1), [self.image_size, self.image_size])
+                gan_im = self.gan_to_image_size(gan_im.clamp(min=-1, max=1))
             center_w, center_h = self._latent_centers()
             offset, w = self.latent_projection(pseudo, gan_im, latent, center_w, center_h, F1_d)
             frames = []
             for i in range(0, V, gan_batch):
                 j = slice(i, i + gan_batch)
                 projected, _ = self.generator.invert(pseudo[j], (offset[j], w[j]), self.truncation, self.mean_latent)
-                frames.append(utils.resize(projected, [self.image_size, self.image_size]))
+                frames.append(self.gan_to_image_size(projected))
         return dict(pseudo=pseudo, mask=mask, gan=torch.cat(frames, 0), w=w, view=d["view"], light=d["light"])
 
     # ------------------------------------------------------------------ step 3

@@ -273,7 +273,7 @@ def main(argv=None, model=None, masking_model=None):
         from .renderer import Renderer
         renderer = Renderer(config, config["image_size"], MIN_DEPTH, MAX_DEPTH, device=device)
     dataset = ImageDataset(os.path.join(config["root_path"], category), subset=args.images,
-                           transform=default_transform(config["image_size"]))
+                           transform=default_transform(config["image_size"], config.get("crop"), config.get("origin_size")))
     written = []
     for i, stem in enumerate(_stems(dataset)):
         image = dataset[i].to(device)

@@ -1106,6 +1106,32 @@ int g2s_canon_mask(const float *depth, const float *rays, const float *R, const 
                    float rot_center_depth, const float *mask, float *out, int B, int Bm, int H, int W,
                    g2s_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Separable banded resampler (csrc/resample.hip; op/resample.py crop_resize: the centre crop of step 2,
+ * resize -> crop -> resize, and its transpose, each as ONE launch).
+ *
+ * g2s_resample_sep: x [planes, Hin, Win] -> y [planes, Hout, Wout],
+ *     y[p,i,j] = sum_{a < ylen[i]} yw[i*Ky + a] * ( sum_{b < xlen[j]} xw[j*Kx + b] * x[p, ylo[i] + a, xlo[j] + b] ).
+ *   The horizontal sum runs first, then the vertical one, each an ascending fmaf chain from 0; no atomics, no
+ *   workspace: two calls are bit-identical in every mode.  EVERY element of y is written; where ylen[i] == 0 or
+ *   xlen[j] == 0 it is 0.  Only rows and columns inside the bands are read.
+ *   ylo, ylen [Hout] and yw [Hout, Ky], xlo, xlen [Wout] and xw [Wout, Kx] are DEVICE memory (int32 / f32), so the
+ *   launcher cannot look into them: it refuses NULL pointers, sizes < 1, Ky or Kx outside 1..g2s_resample_max_taps()
+ *   (8), and shapes whose one-row tile does not fit 64 KB of LDS (g2s_resample_tile_rows(...) == 0).  The bands
+ *   themselves are checked once, on the host copy, by g2s_resample_bands_check below; the kernel skips a tap outside
+ *   the input, so an unchecked table gives wrong values, never an out-of-bounds access.
+ * g2s_resample_bands_check: HOST tables lo, len [n_out] of K-tap bands over an input of n_in positions.  Refuses
+ *   K outside 1..8, len outside 0..K, a band that leaves [0, n_in), and bands that do not ascend or that leave a gap
+ *   between consecutive non-empty ones (the LDS budget of a tile rests on that: tr output rows touch <= tr*K rows).
+ * g2s_resample_tile_rows: output rows per workgroup the launcher picks for a shape (0: does not fit).
+ * ---------------------------------------------------------------------------------------- */
+int g2s_resample_max_taps(void);
+int g2s_resample_tile_rows(int Hin, int Win, int Hout, int Wout, int Ky, int Kx);
+int g2s_resample_bands_check(const int *lo, const int *len, int n_out, int K, int n_in);
+int g2s_resample_sep(const float *x, float *y, int planes, int Hin, int Win, int Hout, int Wout,
+                     const int *ylo, const int *ylen, const float *yw, int Ky,
+                     const int *xlo, const int *xlen, const float *xw, int Kx, g2s_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
