@@ -585,8 +585,9 @@ static int conv_launch(const float *x, const float *w, const float *in_scale, co
     dim3 grid(tiles, splitk, d.ncls);
     // A bias / activation epilogue needs the complete sum: with split-K it runs as a second,
     // elementwise launch (g2s_fused_bias_act in place) after the partial sums have been added.
+    // Holes (k = 1 at stride 2) take that route too: no class writes them, and their value is the tail of 0.
     const bool split = splitk > 1;
-    const bool deferred_epilogue = split && (ep.bias != nullptr || ep.act != 0 || ep.noise != nullptr);
+    const bool deferred_epilogue = (split || holes) && (ep.bias != nullptr || ep.act != 0 || ep.noise != nullptr);
     if (deferred_epilogue) {
         d.bias = nullptr;
         d.noise = d.noise_w = nullptr;

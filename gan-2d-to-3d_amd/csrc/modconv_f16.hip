@@ -20,6 +20,16 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int OOB = 0x7fffffff;  // voffset beyond num_records: the buffer load returns 0
 
+// fl32(x * s): the scaled activation as a float32 number of its own.  The operand is fp16_rtne(fl32(x * s)); a product
+// whose only use is the conversion is selected as one v_fma_mixlo_f16, which rounds the exact product once and differs
+// from the contract wherever the float32 product lands on a tie of two halves.  The empty statement keeps the product
+// in a register of its own (no instruction, no ordering constraint).
+__device__ __forceinline__ float scaled_f32(const float x, const float s) {
+    float p = x * s;
+    asm("" : "+v"(p));
+    return p;
+}
+
 // Reduction channels per K tile.  quad: the pipelined 3x3 form (modconv_f16w_body); else the channels that
 // make K = CPT * T a multiple of 8.
 __host__ __device__ constexpr int f16_cpt(int T, bool quad) {
@@ -182,7 +192,7 @@ __device__ __forceinline__ void modconv_f16_body(const ConvDesc &d, const ConvCl
                 const bool out = (int)((dchB[e] >> (8 * j)) & 0xff) >= left;
                 float v = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(t.rx, out ? OOB : offB[e][j], ch0 * t.HW * 4, 0));
                 if constexpr (SCALE)
-                    v *= __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(t.rsc, out ? OOB : offS[e][j], ch0 * 4, 0));
+                    v = scaled_f32(v, __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(t.rsc, out ? OOB : offS[e][j], ch0 * 4, 0)));
                 h[j] = (_Float16)v;
             }
             *reinterpret_cast<f16x4 *>(&Bs[(gidx % BN) * KTP + (gidx / BN) * 4]) = h;
@@ -341,7 +351,7 @@ __device__ __forceinline__ void modconv_f16p_body(const ConvDesc &d, const ConvC
         for (int e = 0; e < GB; e++) {
             f16x4 h;
 #pragma unroll
-            for (int j = 0; j < 4; j++) h[j] = (_Float16)(SCALE ? rb[e][j] * rsv[SCALE ? e : 0][j] : rb[e][j]);
+            for (int j = 0; j < 4; j++) h[j] = (_Float16)(SCALE ? scaled_f32(rb[e][j], rsv[SCALE ? e : 0][j]) : rb[e][j]);
             *reinterpret_cast<f16x4 *>(&bbuf[t.nB * KTP + ((tid + e * NTHREADS) / BN) * 4]) = h;
         }
     };
@@ -434,9 +444,9 @@ __device__ __forceinline__ void modconv_f16w_body(const ConvDesc &d, const ConvC
             float e2 = left ? l1 : (right ? 0.0f : l2);
             if constexpr (SCALE) {
                 const float sc = dchB[e] == 0 ? rs[0] : dchB[e] == 1 ? rs[1] : dchB[e] == 2 ? rs[2] : rs[3];
-                e0 *= sc;
-                e1 *= sc;
-                e2 *= sc;
+                e0 = scaled_f32(e0, sc);
+                e1 = scaled_f32(e1, sc);
+                e2 = scaled_f32(e2, sc);
             }
             f16x4 h;
             h[0] = (_Float16)(rev ? e2 : e0);

@@ -19,7 +19,8 @@ Labels of a convolution launch:
   split:1 / split:n                      split-K after clipping to kt_min; split:heuristic / tuned / forced / det say who
                                          chose it, split:clipped that kt_min cut it, split:unequal that the classes of a
                                          strided scatter got different shares (cls_splitk)
-  epilogue:none / kernel / deferred      bias / activation: none, in the kernel, or as a second launch after split-K
+  epilogue:none / kernel / deferred      bias / activation: none, in the kernel, or as a second launch (after split-K, and
+                                         where classes leave holes, whose value is the tail of 0)
   holes                                  output positions no class writes (k = 1, stride 2 scatter)
   needs-zero / overwrites                whether the launch adds into a cleared y
   layout:adj0:mm1 ..                     adjoint x w_m_major;  groups1 ..
@@ -147,9 +148,10 @@ def classes(H, W, k, s, p, adjoint, out_h=0, out_w=0):
 
 
 def plan_conv(B, Cr, M, H, W, k, s, p, adjoint, m_major, out_h=0, out_w=0, groups=1, fused=False, tile=-1, splitk=-1,
-              det=False, rider=False):
+              det=False, rider=False, tuned=True):
     """What conv2d_impl + conv_launch decide for one g2s_conv2d call under g2s_modconv_tune(tile, splitk) and the
-    deterministic flag `det`.  Raises Rejected for a tap count without a body."""
+    deterministic flag `det`.  Raises Rejected for a tap count without a body.  tuned = False: conv_launch alone, without
+    conv2d_impl's table (the callers of tests/modconv_cases.py, whose entry points do not read it)."""
     assert 1 <= k <= 5 and s in (1, 2) and 0 <= p < k and 1 <= groups <= 8
     OHf, OWf, cls, holes = classes(H, W, k, s, p, adjoint, out_h if adjoint else 0, out_w if adjoint else 0)
     for c in cls:
@@ -161,7 +163,7 @@ def plan_conv(B, Cr, M, H, W, k, s, p, adjoint, m_major, out_h=0, out_w=0, group
     kt_min, kt_max = min(kts), max(max(kts), 1)
     # conv2d_impl: the measured table, square inputs only
     t_tile, t_split = -1, -1
-    if H == W:
+    if H == W and tuned:
         t_tile, t_split = tuned_rows().get((B, Cr, M, H, k, s, p, int(bool(adjoint)), int(bool(m_major)), int(bool(fused)),
                                             groups), (-1, -1))
     pick, source = 2, "heuristic"
@@ -198,7 +200,7 @@ def plan_conv(B, Cr, M, H, W, k, s, p, adjoint, m_major, out_h=0, out_w=0, group
     return dict(OHf=OHf, OWf=OWf, classes=cls, holes=holes, big=big, kmax=26 if big else 18,
                 partial=[Cr % cpt_of(c["T"]) != 0 for c in cls], ktiles=kts, kt_min=kt_min, pick=pick, source=source,
                 BM=BM, BN=BN, tiles=tiles, nmax=nmax, splitk=sk, asked=asked, split_source=sk_source,
-                cls_splitk=cls_splitk, atomic=[c > 1 for c in cls_splitk], deferred=split and bool(fused),
+                cls_splitk=cls_splitk, atomic=[c > 1 for c in cls_splitk], deferred=(split or bool(holes)) and bool(fused),
                 needs_zero=split or bool(holes), one_grid=bool(rider) and pick >= 2)
 
 
