@@ -18,6 +18,7 @@ Conscious differences (none changes a returned value):
   * offline: a missing `gan_ckpt_path` / `view_mvn_path` / `light_mvn_path` falls back to
     random-init G/D and to the `view_mvn` / `light_mvn` entries of the config (mean, cov lists).
 """
+import collections
 import datetime
 import logging
 import math
@@ -38,6 +39,10 @@ from .stylegan2 import Discriminator, Generator
 
 
 _WSUM_CONST = {}
+
+# what GAN2Shape._reconstruct hands back
+Reconstruction = collections.namedtuple(
+    "Reconstruction", "normal light_a light_b diffuse_shading recon_im recon_im_mask recon_depth")
 
 
 def weighted_total(terms):
@@ -306,89 +311,63 @@ class GAN2Shape(nn.Module):
                 t.record_stream(main)
         return outs
 
-    # ------------------------------------------------------------------ step 1
-    def forward_step1(self, images, latents, collected, step1=True, eval=False, object_mask=None, **kwargs):
-        """model.py:95-173: optimise the albedo net (step1=True) / everything (step1=False).
+    # ------------------------------------------------------------------ the parts steps 1 and 3 are made of
+    def _run_nets(self, images, step1, vl_input=None):
+        """The four nets -> (depth_raw, albedo, view, lighting).  D and A read `images`; V and L read `vl_input`
+        (default `images`; step 3 hands them the image and its projected samples in one batch).  In step 1 only the
+        albedo net learns (model.py:99-122): D, V and L run under no_grad."""
+        vl = images if vl_input is None else vl_input
 
-        object_mask: the object mask of `images`, (B,1,S,S) or (1,1,S,S) float in [0, 1]; required when the masks are
-        live (`masks_live`), ignored otherwise.  The canonical mask made from it (Renderer.canon_mask of the
-        unflipped canonical depth under the step's view) goes into the last slot of `collected`; the step's own
-        loss terms do not read it.
-
-        `_nets`, `_defer_perc` are internal (forward_step3 batches the image with its projected
-        samples through V / L and through LPIPS; the arithmetic per sample is unchanged)."""
-        b = 1
-        h, w = self.image_size, self.image_size
-        live = self.masks_live and not eval
-        if live and object_mask is None:
-            raise ValueError("object_mask is on (config object_mask and use_mask): forward_step1 / forward_step3 need "
-                             "object_mask=, the object mask of the image (B,1,S,S)")
-        if eval:
-            zeropool.end()      # evaluation is no training step: nothing of it is served from (or left in) a step's pool
-        elif step1 and images.is_cuda:   # a step of its own (forward_step3 begins the pool for its inner call)
-            zeropool.begin(1, images.device)
-
-        def frozen_if_step1(net, x):  # model.py:99-122: only the albedo net learns in step 1
+        def frozen_if_step1(fn, *args):
             def job():
                 with self._no_grad_if(step1):
-                    return net(x)
+                    return fn(*args)
             return job
 
-        pre = kwargs.get('_nets')
-        if pre is None and self.paired_nets:
-            def vl_pair():
-                with self._no_grad_if(step1):
-                    return networks.forward_pair(self.viewpoint_net, self.lighting_net, images)
-            # the two paired passes read the same image and nothing else: two branches when parallel_nets is on
+        if self.paired_nets:
+            # the two paired passes read nothing of each other: two branches when parallel_nets is on
             (depth_raw, albedo), (view, lighting) = self._fork([
-                lambda: networks.forward_pair(self.depth_net, self.albedo_net, images, train_a=not step1), vl_pair])
+                lambda: networks.forward_pair(self.depth_net, self.albedo_net, images, train_a=not step1),
+                frozen_if_step1(networks.forward_pair, self.viewpoint_net, self.lighting_net, vl)])
             if step1:
                 depth_raw = depth_raw.detach()
-        elif pre is None:  # the four nets read the same image and nothing else: independent chains
-            depth_raw, albedo, view, lighting = self._fork([
-                frozen_if_step1(self.depth_net, images), lambda: self.albedo_net(images),
-                frozen_if_step1(self.viewpoint_net, images), frozen_if_step1(self.lighting_net, images)])
-        else:
-            depth_raw, albedo, view, lighting = pre
-        depth = self.get_clamped_depth(depth_raw.squeeze(1), h, w)
-        view = view + self.view_light_sampler.view_mean.unsqueeze(0)
-        lighting = lighting + self.view_light_sampler.light_mean.unsqueeze(0)
-        flip = bool(self.flip1 if step1 else self.flip3) and not eval
-        canon_mask = None if len(images) == 1 else [None] * len(images)
-        if live:    # from the unflipped canonical depth under the step's view, whichever branch follows
-            self._set_view(view)
-            canon_mask = self.renderer.canon_mask(depth, object_mask)
-            if len(images) > 1:
-                canon_mask = list(canon_mask.split(1))
-        if flip:
-            return self._step1_flipped(images, depth, albedo, view, lighting, b, kwargs.get('_defer_perc'), canon_mask)
-        if not live:
-            self._set_view(view)
+            return depth_raw, albedo, view, lighting
+        return self._fork([     # four independent chains
+            frozen_if_step1(self.depth_net, images), lambda: self.albedo_net(images),
+            frozen_if_step1(self.viewpoint_net, vl), frozen_if_step1(self.lighting_net, vl)])
 
-        normal = self.renderer.get_normal_from_depth(depth)
-        lighting_a, lighting_b, diffuse_shading, texture = self._shade(normal, lighting, albedo)
+    def _add_means(self, view, lighting):
+        """The nets predict offsets from the sampler's means (model.py:118,130)."""
+        return (view + self.view_light_sampler.view_mean.unsqueeze(0),
+                lighting + self.view_light_sampler.light_mean.unsqueeze(0))
 
+    def _canonical(self, depth_raw, view, lighting):
+        """What the nets give -> (canonical depth, view, lighting) as every later stage reads them."""
+        depth = self.get_clamped_depth(depth_raw.squeeze(1), self.image_size, self.image_size)
+        return (depth,) + self._add_means(view, lighting)
+
+    def _reconstruct(self, depth, albedo, view, light, normal=None, masks=None):
+        """The reconstruction pass (model.py:119-148, 246-262): the canonical depth and albedo shaded by `light`,
+        carried to `view` and read back at the input's pixels.  One row per row of `light`; a single canonical shape
+        serves all of them (step 3).  view None: the renderer holds the view already (`_set_view` was called for the
+        canonical mask).  normal None: from `depth`.  masks: multiplied into the reconstruction mask."""
+        if view is not None:
+            self._set_view(view)
+        if normal is None:
+            normal = self.renderer.get_normal_from_depth(depth)
+        light_a, light_b, diffuse_shading, texture = self._shade(normal, light, albedo)
+        if len(depth) != len(light):     # one canonical shape under several views and lights
+            depth = depth.expand(len(light), *depth.shape[1:])
         recon_depth = self.renderer.warp_canon_depth(depth)
         grid_2d_from_canon = self.renderer.get_inv_warped_2d_grid(recon_depth)
         margin = (self.max_depth - self.min_depth) / 2
         # invalid border pixels have been clamped at max_depth+margin
         recon_im_mask = (recon_depth < self.max_depth + margin).float().unsqueeze(1).detach()
+        if masks is not None:
+            recon_im_mask = recon_im_mask * masks
         recon_im = grid_sample(texture, grid_2d_from_canon, -1, 1)   # F.grid_sample(..).clamp(-1, 1), one launch
-        if eval:
-            return recon_im, recon_depth
+        return Reconstruction(normal, light_a, light_b, diffuse_shading, recon_im, recon_im_mask, recon_depth)
 
-        recon_b, mask_b = self._head(recon_im, b), self._head(recon_im_mask, b)   # model.py:150: b = 1
-        loss_l1_im = self.photometric_loss(recon_b, images, mask=mask_b)
-        perc_pair = (recon_b * mask_b, images * mask_b)
-        smooth_terms = [(self.lam_smooth, self.smooth_loss(depth)), (self.lam_smooth, self.smooth_loss(diffuse_shading))]
-        collected = (normal, lighting_a, lighting_b, albedo, depth, canon_mask)
-        if kwargs.get('_defer_perc'):  # caller adds lam_perc * mean(LPIPS(*perc_pair)) and sums the terms
-            return [(1.0, loss_l1_im)] + smooth_terms, collected, perc_pair
-        # loss_total = loss_l1_im + lam_perc * mean(perc) + lam_smooth * (smooth(depth) + smooth(shading))
-        loss_total = weighted_total([(1.0, loss_l1_im), (self.lam_perc, self.perceptual_loss(*perc_pair))] + smooth_terms)
-        return loss_total, collected
-
-    # ------------------------------------------------------------------ symmetry flips
     def _mirror_rows(self, depth, albedo, repeat=1):
         """(depth2, albedo2): `repeat` copies of every sample followed by `repeat` copies of its left-right mirror —
         cat([depth.repeat_interleave(repeat, 0), depth.flip(2).repeat_interleave(repeat, 0)]) and the same of the albedo
@@ -401,74 +380,101 @@ class GAN2Shape(nn.Module):
             return x if repeat == 1 else (x.expand(repeat, *x.shape[1:]) if x.shape[0] == 1 else x.repeat_interleave(repeat, 0))
         return (torch.cat([rows(depth), rows(depth.flip(2))], 0), torch.cat([rows(albedo), rows(albedo.flip(3))], 0))
 
-    def _perc_terms(self, groups):
-        """LPIPS of several (weight of the group's mean, pred, target) groups through ONE trunk pass ->
-        one weighted_total term."""
+    def _half_rows(self, x, n, stride, halves):
+        """Rows 0 .. n of x (the plain pass) and, with two halves, rows stride .. stride + n (its mirror)."""
+        if halves == 1:
+            return [self._head(x, n)]
+        if stride == n:     # one split (a single concatenation in backward) instead of two slices
+            return list(x.split([n, n]))
+        return [x[:n], x[stride:stride + n]]
+
+    def _half_losses(self, recon, target, n, stride, halves, smooth=()):
+        """The loss terms of a reconstruction against `target` over its halves (weight 1, and lam_flip for the
+        mirror) -> (terms for weighted_total: photometric per half and lam_smooth * smooth_loss of every tensor in
+        `smooth`; LPIPS groups [(weight, pred, target)] for `_perc_term`)."""
+        halves_of = list(zip((1.0, self.lam_flip), self._half_rows(recon.recon_im, n, stride, halves),
+                             self._half_rows(recon.recon_im_mask, n, stride, halves)))
+        terms = [(wgt, self.photometric_loss(pred, target, mask=mask)) for wgt, pred, mask in halves_of]
+
+        def smooth_terms():
+            return [(self.lam_smooth, self.smooth_loss(x)) for x in smooth]
+        # the launch order the steps were measured with: the smooth terms precede the masked products of a flipped
+        # pass and follow those of a plain one
+        if halves == 2:
+            terms += smooth_terms()
+        groups = [(wgt, pred * mask, target * mask) for wgt, pred, mask in halves_of]
+        if halves == 1:
+            terms += smooth_terms()
+        return terms, groups
+
+    def _perc_term(self, groups):
+        """lam_perc * sum over the (weight, pred, target) groups of weight * mean(LPIPS(pred, target)) as one
+        weighted_total term; several groups go through ONE trunk pass."""
+        if len(groups) == 1:    # as it stands: no concatenation, and LPIPS pairs one prediction with several targets itself
+            (wgt, pred, target), = groups
+            return self.lam_perc * wgt, self.perceptual_loss(pred, target)
         preds, targets, weights = [], [], ()
         for wgt, pred, target in groups:
             n = max(len(pred), len(target))
             preds.append(pred if len(pred) == n else pred.expand(n, *pred.shape[1:]))
             targets.append(target if len(target) == n else target.expand(n, *target.shape[1:]))
-            weights += (wgt / n,) * n
+            weights += (self.lam_perc * wgt / n,) * n
         return weights, self.perceptual_loss(torch.cat(preds, 0), torch.cat(targets, 0)).reshape(-1)
 
-    def _step1_flipped(self, images, depth, albedo, view, lighting, b, defer_perc, canon_mask=None):
-        """The rest of forward_step1 with the symmetry flip on: rows 0 .. B of every tensor are the plain pass, rows
-        B .. 2B the canonical depth and albedo mirrored left-right under the same view and light.
-        loss_total = l1 + lam_flip * l1_flip + lam_perc * (perc + lam_flip * perc_flip)
-                     + lam_smooth * (smooth(depth2) + smooth(diffuse_shading2));
-        `collected` holds the B plain rows only; `canon_mask` (its last slot) is handed through as forward_step1 made
-        it from the unflipped depth."""
+    # ------------------------------------------------------------------ step 1
+    def _step1_terms(self, images, nets, step1, object_mask=None):
+        """Step 1 behind the nets: `nets` = (depth_raw, albedo, view, lighting) of `images` -> (terms of
+        weighted_total without LPIPS, collected, LPIPS groups for `_perc_term`).  With the symmetry flip on (flip1 for
+        step1=True, flip3 for the inner pass of step 3) rows B .. 2B of the reconstruction are the canonical depth and
+        albedo mirrored left-right under the same view and light, held to the same image with weight lam_flip;
+        `collected` holds the B plain rows either way, and the canonical mask comes from the unflipped depth."""
+        b = 1       # model.py:150: only the first reconstruction enters the loss
         B = len(images)
-        depth2, albedo2 = self._mirror_rows(depth, albedo)
-        view2, lighting2 = torch.cat([view, view], 0), torch.cat([lighting, lighting], 0)
-        self._set_view(view2)
-        normal2 = self.renderer.get_normal_from_depth(depth2)
-        lighting_a, lighting_b, diffuse_shading2, texture2 = self._shade(normal2, lighting2, albedo2)
-        recon_depth = self.renderer.warp_canon_depth(depth2)
-        grid_2d_from_canon = self.renderer.get_inv_warped_2d_grid(recon_depth)
-        margin = (self.max_depth - self.min_depth) / 2
-        recon_im_mask = (recon_depth < self.max_depth + margin).float().unsqueeze(1).detach()
-        recon_im = grid_sample(texture2, grid_2d_from_canon, -1, 1)
-        if B == b:      # one split (a single concatenation in backward) instead of two slices
-            (recon_b, recon_f), (mask_b, mask_f) = recon_im.split([b, b]), recon_im_mask.split([b, b])
-        else:
-            recon_b, recon_f, mask_b, mask_f = recon_im[:b], recon_im[B:B + b], recon_im_mask[:b], recon_im_mask[B:B + b]
-        terms = [(1.0, self.photometric_loss(recon_b, images, mask=mask_b)),
-                 (self.lam_flip, self.photometric_loss(recon_f, images, mask=mask_f)),
-                 (self.lam_smooth, self.smooth_loss(depth2)), (self.lam_smooth, self.smooth_loss(diffuse_shading2))]
-        perc = [(1.0, recon_b * mask_b, images * mask_b), (self.lam_flip, recon_f * mask_f, images * mask_f)]
-        collected = (normal2[:B], lighting_a[:B], lighting_b[:B], albedo, depth, canon_mask)
-        if defer_perc:  # the caller runs LPIPS on these groups with its own and sums the terms
-            return terms, collected, perc
-        terms.append(self._perc_terms([(self.lam_perc * wgt, p, t) for wgt, p, t in perc]))
-        return weighted_total(terms), collected
+        depth_raw, albedo, view, lighting = nets
+        depth, view, lighting = self._canonical(depth_raw, view, lighting)
+        halves = 2 if (self.flip1 if step1 else self.flip3) else 1
+        canon_mask = None if B == 1 else [None] * B
+        rows = (depth, albedo, view, lighting)
+        if self.masks_live:
+            self._set_view(view)
+            canon_mask = self.renderer.canon_mask(depth, object_mask)
+            if B > 1:
+                canon_mask = list(canon_mask.split(1))
+            rows = (depth, albedo, None, lighting)
+        if halves == 2:
+            rows = self._mirror_rows(depth, albedo) + (torch.cat([view, view], 0), torch.cat([lighting, lighting], 0))
+        recon = self._reconstruct(*rows)
+        terms, groups = self._half_losses(recon, images, b, B, halves, smooth=(rows[0], recon.diffuse_shading))
+        collected = (self._head(recon.normal, B), self._head(recon.light_a, B), self._head(recon.light_b, B),
+                     albedo, depth, canon_mask)
+        return terms, collected, groups
 
-    def _step3_flipped(self, step1_loss, perc1, depth, albedo, view, light, projected_samples, masks):
-        """The projected-sample half of forward_step3 with flip3 on: rows 0 .. b render the canonical depth and albedo
-        under the b predicted views and lights, rows b .. 2b their left-right mirror under the same b views and lights;
-        both halves are compared with `projected_samples`.
-        loss_total = step1_loss + l1 + lam_flip * l1_flip + lam_perc * (perc + lam_flip * perc_flip)."""
-        b = len(projected_samples)
-        depth2, albedo2 = self._mirror_rows(depth, albedo, b)
-        view2, light2, masks2 = torch.cat([view, view], 0), torch.cat([light, light], 0), torch.cat([masks, masks], 0)
-        self._set_view(view2)
-        normal2 = self.renderer.get_normal_from_depth(depth2)
-        _, _, _, texture2 = self._shade(normal2, light2, albedo2)
-        recon_depth = self.renderer.warp_canon_depth(depth2)
-        grid_2d_from_canon = self.renderer.get_inv_warped_2d_grid(recon_depth)
-        margin = (self.max_depth - self.min_depth) / 2
-        recon_im_mask = (recon_depth < self.max_depth + margin).float().unsqueeze(1).detach() * masks2
-        recon_im = grid_sample(texture2, grid_2d_from_canon, -1, 1)
-        (recon_b, recon_f), (mask_b, mask_f) = recon_im.split([b, b]), recon_im_mask.split([b, b])
-        l1 = self.photometric_loss(recon_b, projected_samples, mask=mask_b)
-        l1_flip = self.photometric_loss(recon_f, projected_samples, mask=mask_f)
-        perc = [(1.0, recon_b * mask_b, projected_samples * mask_b), (self.lam_flip, recon_f * mask_f, projected_samples * mask_f)]
-        if perc1 is not None:   # step1_loss arrives as its list of terms, its LPIPS groups join this pass's in one trunk pass
-            groups = [(self.lam_perc * wgt, p, t) for wgt, p, t in list(perc1) + perc]
-            return weighted_total(step1_loss + [(1.0, l1), (self.lam_flip, l1_flip), self._perc_terms(groups)])
-        loss_perc = sum(wgt * torch.mean(self.perceptual_loss(p, t)) for wgt, p, t in perc)
-        return step1_loss + l1 + self.lam_flip * l1_flip + self.lam_perc * loss_perc
+    def forward_step1(self, images, latents, collected, step1=True, eval=False, object_mask=None, **kwargs):
+        """model.py:95-173: optimise the albedo net (step1=True) / everything (step1=False) -> (loss, collected);
+        eval=True -> (recon_im, recon_depth) of the plain pass, no loss.
+
+        object_mask: the object mask of `images`, (B,1,S,S) or (1,1,S,S) float in [0, 1]; required when the masks are
+        live (`masks_live`), ignored otherwise.  The canonical mask made from it (Renderer.canon_mask of the
+        unflipped canonical depth under the step's view) goes into the last slot of `collected`; the step's own
+        loss terms do not read it."""
+        if self.masks_live and not eval and object_mask is None:
+            raise ValueError("object_mask is on (config object_mask and use_mask): forward_step1 / forward_step3 need "
+                             "object_mask=, the object mask of the image (B,1,S,S)")
+        if eval:
+            zeropool.end()      # evaluation is no training step: nothing of it is served from (or left in) a step's pool
+        elif step1 and images.is_cuda:   # a step of its own (forward_step3 begins the pool for its inner pass)
+            zeropool.begin(1, images.device)
+        nets = self._run_nets(images, step1)
+        if eval:
+            depth, view, lighting = self._canonical(nets[0], nets[2], nets[3])
+            recon = self._reconstruct(depth, nets[1], view, lighting)
+            return recon.recon_im, recon.recon_depth
+        terms, collected, groups = self._step1_terms(images, nets, step1, object_mask)
+        # loss_total = l1 + lam_perc * mean(perc) + lam_smooth * (smooth(depth) + smooth(shading)), the mirror's l1 and
+        # perc with weight lam_flip.  The place of the LPIPS term (second in a plain pass, last in a flipped one) fixes
+        # the order of the additions, and with it the last bits of the loss
+        terms.insert(1 if len(groups) == 1 else len(terms), self._perc_term(groups))
+        return weighted_total(terms), collected
 
     # ------------------------------------------------------------------ step 2
     def _latent_centers(self):
@@ -481,7 +487,6 @@ class GAN2Shape(nn.Module):
 
     def forward_step2(self, image, latent, collected, n_proj_samples=8, **kwargs):
         """model.py:175-223: optimise the offset encoder so that G reproduces the pseudo samples."""
-        F1_d = 2  # number of mapping network layers used to regularize the latent offset
         if image.is_cuda:
             zeropool.begin(2, image.device)
         *tensors, canon_mask = collected
@@ -491,15 +496,7 @@ class GAN2Shape(nn.Module):
             pseudo_im, mask = self.sample_pseudo_imgs(n_proj_samples, normal, light_a, light_b,
                                                       albedo, depth, canon_mask,
                                                       _draws=kwargs.get('_draws'))
-            gan_im = None
-            if self.relative_encoding:
-                gan_im, _ = self.generator([latent], input_is_w=True,
-                                           truncation_latent=self.mean_latent,
-                                           truncation=self.truncation, randomize_noise=False)
-                gan_im = self.gan_to_image_size(gan_im.clamp(min=-1, max=1))
-            center_w, center_h = self._latent_centers()
-
-        latent_projection = self.latent_projection(pseudo_im, gan_im, latent, center_w, center_h, F1_d)
+        latent_projection = self._project_latent(pseudo_im, latent)
         projected_image, offset = self.generator.invert(pseudo_im, latent_projection,
                                                         self.truncation, self.mean_latent)
         projected_image = self.gan_to_image_size(projected_image)
@@ -509,6 +506,20 @@ class GAN2Shape(nn.Module):
         self.loss_latent_norm = torch.mean(offset ** 2)
         loss_total = weighted_total([(1.0, self.loss_l1), (1.0, self.loss_rec), (self.lam_regular, self.loss_latent_norm)])
         return loss_total, (projected_image.detach(), mask.detach())
+
+    def _project_latent(self, pseudo_im, latent):
+        """(offset, latent + offset) of the pseudo images (model.py:193-205): G's own image of `latent` under
+        `relative_encoding`, the latent centres (both without gradient), then latent_projection."""
+        F1_d = 2  # number of mapping network layers used to regularize the latent offset
+        with torch.no_grad():
+            gan_im = None
+            if self.relative_encoding:
+                gan_im, _ = self.generator([latent], input_is_w=True,
+                                           truncation_latent=self.mean_latent,
+                                           truncation=self.truncation, randomize_noise=False)
+                gan_im = self.gan_to_image_size(gan_im.clamp(min=-1, max=1))
+            center_w, center_h = self._latent_centers()
+        return self.latent_projection(pseudo_im, gan_im, latent, center_w, center_h, F1_d)
 
     def latent_projection(self, image, gan_im, latent, center_w, center_h, F1_d):
         """model.py:282-289."""
@@ -585,19 +596,15 @@ class GAN2Shape(nn.Module):
         """The head of forward_step1 without its losses, under no_grad: the four nets on `image` (1,3,S,S) ->
         dict(collected=(normal, light_a, light_b, albedo, depth, canon_mask) as forward_step1 returns it, view (1,6)
         and light (1,4): the predicted view and lighting with the sampler's means added, as the nets give them).
-        forward_step1 itself is not called: it would run the losses and begin a training step's pool, and it does
-        not hand out the raw view and lighting.  This is therefore a second statement of its head (each net called
-        on its own, not through the paired or forked routes, which differ in rounding only) and HAS TO FOLLOW any
-        change made there; tests/test_gpu_manipulate.py holds the two to each other.
+        Each net is called on its own, not through the paired or forked routes of `_run_nets` (which differ in
+        rounding only); everything behind the nets is forward_step1's own code (`_canonical`), without the
+        reconstruction and the losses.
         object_mask (1,1,S,S), optional: the object mask of `image`; when given, canon_mask is Renderer.canon_mask of
         the canonical depth under the predicted view, as forward_step1 makes it with the masks live (an explicit
         request here: the config switch governs the training steps)."""
         with torch.no_grad():
-            h = w = self.image_size
-            depth = self.get_clamped_depth(self.depth_net(image).squeeze(1), h, w)
-            albedo = self.albedo_net(image)
-            view = self.viewpoint_net(image) + self.view_light_sampler.view_mean.unsqueeze(0)
-            light = self.lighting_net(image) + self.view_light_sampler.light_mean.unsqueeze(0)
+            depth_raw, albedo = self.depth_net(image), self.albedo_net(image)
+            depth, view, light = self._canonical(depth_raw, self.viewpoint_net(image), self.lighting_net(image))
             normal = self.renderer.get_normal_from_depth(depth)
             ab = light[:, :2] / 2 + 0.5
             canon_mask = None
@@ -618,7 +625,6 @@ class GAN2Shape(nn.Module):
         every frame and comes back as `mask`.
         Under no_grad.  Returns dict(pseudo (V,3,S,S) the rendered frames, mask (V,1,S,S), gan (V,3,S,S) the GAN's
         images resized to image_size, w (V,style_dim) = latent + offset, view (1,6), light (1,4) the predictions)."""
-        F1_d = 2
         gan_batch = int(gan_batch)
         if gan_batch < 1:
             raise ValueError("gan_batch must be at least 1")
@@ -638,13 +644,7 @@ class GAN2Shape(nn.Module):
             pseudo, mask = self.renderer.render_pseudo_sweep(albedo, normal, depth, views, lights, canon_mask,
                                                              base_view=base)
             pseudo, mask = pseudo[0], mask[0]
-            gan_im = None
-            if self.relative_encoding:
-                gan_im, _ = self.generator([latent], input_is_w=True, truncation_latent=self.mean_latent,
-                                           truncation=self.truncation, randomize_noise=False)
-                gan_im = self.gan_to_image_size(gan_im.clamp(min=-1, max=1))
-            center_w, center_h = self._latent_centers()
-            offset, w = self.latent_projection(pseudo, gan_im, latent, center_w, center_h, F1_d)
+            offset, w = self._project_latent(pseudo, latent)
             frames = []
             for i in range(0, V, gan_batch):
                 j = slice(i, i + gan_batch)
@@ -656,7 +656,9 @@ class GAN2Shape(nn.Module):
     def forward_step3(self, images, latents, collected, object_mask=None, **kwargs):
         """model.py:225-280: optimise V, L, D, A on the image and its projected samples.  object_mask: as in
         forward_step1, for the inner step-1 pass; step 2's `masks` (which carry the warped canonical mask) multiply
-        into the reconstruction mask as they always did."""
+        into the reconstruction mask as they always did.  With flip3 on, rows b .. 2b of the reconstruction are the
+        canonical depth and albedo mirrored left-right under the same b predicted views and lights; both halves are
+        compared with the projected samples, the mirror with weight lam_flip."""
         projected_samples, masks = collected
         if self.masks_live and object_mask is None:      # before any work: the inner step-1 pass would refuse it
             raise ValueError("object_mask is on (config object_mask and use_mask): forward_step3 needs object_mask=, the "
@@ -668,58 +670,36 @@ class GAN2Shape(nn.Module):
         torch.randperm(len(projected_samples))
         projected_samples, masks = projected_samples.to(self.device), masks.to(self.device)
 
-        # V and L see the image and its projected samples in ONE batch (1 + n), and so does LPIPS
-        # below: the reference runs them as two calls each (model.py:113-131,243-250 and :159,275);
-        # per-sample results are unchanged (no batch statistics in these nets), launches halve.
         b = len(projected_samples)
-        both = torch.cat([images[:1], projected_samples], 0) if len(images) == 1 else None
-        if both is not None:
-            if self.paired_nets:
-                (depth_raw, albedo1), (view_all, light_all) = self._fork([
-                    lambda: networks.forward_pair(self.depth_net, self.albedo_net, images),
-                    lambda: networks.forward_pair(self.viewpoint_net, self.lighting_net, both)])
-            else:
-                depth_raw, albedo1, view_all, light_all = self._fork([
-                    lambda: self.depth_net(images), lambda: self.albedo_net(images),
-                    lambda: self.viewpoint_net(both), lambda: self.lighting_net(both)])
+        batched = len(images) == 1
+        if batched:
+            # V and L see the image and its projected samples in ONE batch (1 + n), and so does LPIPS
+            # below: the reference runs them as two calls each (model.py:113-131,243-250 and :159,275);
+            # per-sample results are unchanged (no batch statistics in these nets), launches halve.
+            depth_raw, albedo1, view_all, light_all = self._run_nets(images, False, torch.cat([images, projected_samples], 0))
             # one split each (a single concatenation in backward) instead of two slices (a zero-fill
             # + copy each)
             view1, view = view_all.split([1, b])
             light1, light = light_all.split([1, b])
-            step1_loss, collected, perc1 = self.forward_step1(
-                images, None, None, step1=False, _nets=(depth_raw, albedo1, view1, light1),
-                _defer_perc=True, object_mask=object_mask)
-        else:
+            terms, collected, groups1 = self._step1_terms(images, (depth_raw, albedo1, view1, light1), False, object_mask)
+        else:       # several images: the reference's two calls and its sums
             step1_loss, collected = self.forward_step1(images, None, None, step1=False, object_mask=object_mask)
-            perc1 = None
             view, light = self.viewpoint_net(projected_samples), self.lighting_net(projected_samples)
         normal, _, _, albedo, depth, _ = collected
 
-        view = view + self.view_light_sampler.view_mean.unsqueeze(0)
-        light = light + self.view_light_sampler.light_mean.unsqueeze(0)
-        if self.flip3:
-            return self._step3_flipped(step1_loss, perc1, depth, albedo, view, light, projected_samples, masks), None
-        self._set_view(view)
-        _, _, diffuse_shading, texture = self._shade(normal, light, albedo)
-
-        depth = depth.expand(b, self.image_size, self.image_size)
-        recon_depth = self.renderer.warp_canon_depth(depth)
-        grid_2d_from_canon = self.renderer.get_inv_warped_2d_grid(recon_depth)
-        margin = (self.max_depth - self.min_depth) / 2
-        recon_im_mask = (recon_depth < self.max_depth + margin).float().unsqueeze(1).detach() * masks
-        recon_im = grid_sample(texture, grid_2d_from_canon, -1, 1)   # F.grid_sample(..).clamp(-1, 1), one launch
-
-        recon_b, mask_b = self._head(recon_im, b), self._head(recon_im_mask, b)
-        loss_l1_im = self.photometric_loss(recon_b, projected_samples, mask=mask_b)
-        pred, target = recon_b * mask_b, projected_samples * mask_b
-        if perc1 is not None:
-            # step1_loss arrives as its list of terms; LPIPS ran once on (image, n samples): its first entry
-            # is the inner step-1 term (mean over 1), the other b the projected samples' (mean over b)
-            perc = self.perceptual_loss(torch.cat([perc1[0], pred], 0), torch.cat([perc1[1], target], 0)).reshape(-1)
-            terms = step1_loss + [(1.0, loss_l1_im), ((self.lam_perc,) + (self.lam_perc / b,) * b, perc)]
-            return weighted_total(terms), None
-        loss_perc_im = torch.mean(self.perceptual_loss(pred, target))
-        return step1_loss + loss_l1_im + self.lam_perc * loss_perc_im, None
+        view, light = self._add_means(view, light)
+        halves = 2 if self.flip3 else 1
+        if halves == 2:     # the normals of the mirrored rows come from the mirrored depth
+            (depth, albedo), normal = self._mirror_rows(depth, albedo, b), None
+            view, light, masks = torch.cat([view, view], 0), torch.cat([light, light], 0), torch.cat([masks, masks], 0)
+        recon = self._reconstruct(depth, albedo, view, light, normal, masks)
+        l1_terms, groups = self._half_losses(recon, projected_samples, b, b, halves)
+        if batched:     # LPIPS once on the inner pass's groups (mean over 1 each) and this pass's (mean over b each)
+            return weighted_total(terms + l1_terms + [self._perc_term(groups1 + groups)]), None
+        loss = step1_loss
+        for wgt, l1 in l1_terms:
+            loss = loss + wgt * l1
+        return loss + self.lam_perc * sum(wgt * torch.mean(self.perceptual_loss(p, t)) for wgt, p, t in groups), None
 
     # ------------------------------------------------------------------ evaluation / checkpoints
     def evaluate_results(self, image):

@@ -124,17 +124,17 @@ def run_pass(model, name, image, latent, c2, evidence, zero_grads):
             loss, collected = model.forward_step1(image, latent, None, step1=step1)
         else:
             inner = {}
-            f1 = model.forward_step1
+            f1 = model._step1_terms       # the inner step-1 pass of step 3 -> (terms, collected, LPIPS groups)
 
             def keep(*a, **k):
                 r = f1(*a, **k)
                 inner["collected"] = r[1]
                 return r
-            model.forward_step1 = keep
+            model._step1_terms = keep
             try:
                 loss, _ = model.forward_step3(image, latent, c2)
             finally:
-                del model.forward_step1
+                del model._step1_terms
             collected = inner["collected"]
         loss.backward()
     finally:

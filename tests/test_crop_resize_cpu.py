@@ -151,9 +151,12 @@ def test_with_crop_the_model_takes_the_composition_on_the_cpu():
 
 
 def test_model_source_routes_every_gan_resize_through_the_switch():
-    """forward_step2 (projected image, and the GAN image under relative_encoding) and both sites of manipulate."""
+    """The projected image of forward_step2, the frames of manipulate, and the GAN image under relative_encoding,
+    which both take from _project_latent."""
     import inspect
     from gan2shape_amd.model import GAN2Shape
-    for fn, n in ((GAN2Shape.forward_step2, 2), (GAN2Shape.manipulate, 2)):
+    for fn in (GAN2Shape.forward_step2, GAN2Shape.manipulate):
+        assert inspect.getsource(fn).count("self._project_latent(") == 1
+    for fn, n in ((GAN2Shape.forward_step2, 1), (GAN2Shape.manipulate, 1), (GAN2Shape._project_latent, 1)):
         src = inspect.getsource(fn)
         assert src.count("self.gan_to_image_size(") == n and "utils.resize(" not in src

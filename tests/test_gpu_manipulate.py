@@ -241,6 +241,29 @@ def test_manipulate_vs_reference_run(step_model):
     assert flips < 2e-3
 
 
+def test_decompose_is_forward_step1_behind_the_nets(step_model):
+    """With every net called on its own in both (paired_nets off) and reproducible launch partitions, decompose and
+    forward_step1 run the same code on the same numbers: the same bits."""
+    from gan2shape_amd import lib, zeropool
+    m, g = step_model
+    image, latent = _dev(g["image"]), _dev(g["latent"])
+    paired, m.paired_nets = m.paired_nets, False
+    prev = lib.set_deterministic(True)
+    try:
+        with torch.no_grad():
+            d = m.decompose(image)
+            _, c1 = m.forward_step1(image, latent, None)
+            view = m.viewpoint_net(image) + m.view_light_sampler.view_mean.unsqueeze(0)
+            light = m.lighting_net(image) + m.view_light_sampler.light_mean.unsqueeze(0)
+        for key, got, want in zip(("normal", "light_a", "light_b", "albedo", "depth"), d["collected"][:5], c1[:5]):
+            assert torch.equal(got, want), key
+        assert torch.equal(d["view"], view) and torch.equal(d["light"], light)
+    finally:
+        lib.set_deterministic(prev)
+        m.paired_nets = paired
+        zeropool.end()
+
+
 def test_manipulate_gan_batch_and_relative(step_model):
     m, g = step_model
     image, latent = _dev(g["image"]), _dev(g["latent"])

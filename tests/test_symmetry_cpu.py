@@ -118,6 +118,19 @@ def test_eval_ignores_the_flip(cpu_case, float64_default):
         m.flip1 = m.flip3 = False
 
 
+def test_decompose_is_forward_step1_behind_the_nets(cpu_case, float64_default):
+    m, g, image, c2 = cpu_case          # paired_nets is False on this model: both call each net on its own
+    assert m.paired_nets is False
+    with torch.no_grad():
+        d = m.decompose(image)
+        _, c1 = m.forward_step1(image, None, None)
+        view = m.viewpoint_net(image) + m.view_light_sampler.view_mean.unsqueeze(0)
+        light = m.lighting_net(image) + m.view_light_sampler.light_mean.unsqueeze(0)
+    for key, got, want in zip(sc.COLLECTED, d["collected"][:5], c1[:5]):
+        assert torch.equal(got, want), key
+    assert torch.equal(d["view"], view) and torch.equal(d["light"], light)
+
+
 class RecordingModel(mc.ToyStepModel):
     """The toy step model of the trainer tests; every step call records (kind, flip1, flip3)."""
 
