@@ -110,10 +110,12 @@ __global__ __launch_bounds__(256) void grid_sample_bwd(const float *__restrict__
             if (c.in_y1 && c.in_x0) scatter<FIXED>(gx, gfix, o + d.IW, sw * go);
             if (c.in_y1 && c.in_x1) scatter<FIXED>(gx, gfix, o + d.IW + 1, se * go);
         }
-        gix -= v_nw * c.wy0 * go;  giy -= v_nw * c.wx0 * go;
-        gix += v_ne * c.wy0 * go;  giy -= v_ne * c.wx1 * go;
-        gix -= v_sw * c.wy1 * go;  giy += v_sw * c.wx0 * go;
-        gix += v_se * c.wy1 * go;  giy += v_se * c.wx1 * go;
+        // a corner counts only when it is in range, as inside ATen's bounds check: its value is 0 otherwise, but its
+        // weight need not be finite (a NaN or infinite coordinate), and 0 * NaN must not reach ggrid
+        if (c.in_y0 && c.in_x0) { gix -= v_nw * c.wy0 * go;  giy -= v_nw * c.wx0 * go; }
+        if (c.in_y0 && c.in_x1) { gix += v_ne * c.wy0 * go;  giy -= v_ne * c.wx1 * go; }
+        if (c.in_y1 && c.in_x0) { gix -= v_sw * c.wy1 * go;  giy += v_sw * c.wx0 * go; }
+        if (c.in_y1 && c.in_x1) { gix += v_se * c.wy1 * go;  giy += v_se * c.wx1 * go; }
     }
     if (ggrid) {
         float *o = ggrid + ((size_t)b * d.H * d.W + p) * 2;

@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_kernel(const float *x, const
 // The entry of the offset encoder's residual block (GAN2Shape/networks.py:170-194): both branches start
 // from the same x — nn.ReLU() on the residual path, nn.AvgPool2d(2, 2) on the identity path.  One pass
 // writes both; the backward joins the two incoming gradients in one pass as well
-// (gx = ga * (x > 0) + gb / 4), where autograd runs threshold_backward, avg_pool2d_backward and an add.
+// (gx = (x <= 0 ? 0 : ga) + gb / 4, so that a NaN in x passes ga as torch does), where autograd runs threshold_backward, avg_pool2d_backward and an add.
 // Lane = one 2x2 window.  H, W even.
 __global__ __launch_bounds__(256) void res_split_fwd_kernel(const float *__restrict__ x, float *__restrict__ r,
                                                             float *__restrict__ p, long windows, int OH, int OW) {
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(256) void res_split_bwd_kernel(const float *__restr
         ab = *reinterpret_cast<const float2 *>(ga + base + 2 * OW);
     }
     const float q = gb ? gb[i] / 4.0f : 0.0f;
-    auto gate = [](float g, float v) { return v > 0.0f ? g : 0.0f; };
+    auto gate = [](float g, float v) { return v <= 0.0f ? 0.0f : g; };   // torch's threshold_backward: a NaN passes g
     *reinterpret_cast<float2 *>(gx + base) = make_float2(gate(at.x, t.x) + q, gate(at.y, t.y) + q);
     *reinterpret_cast<float2 *>(gx + base + 2 * OW) = make_float2(gate(ab.x, b.x) + q, gate(ab.y, b.y) + q);
 }
@@ -203,11 +203,17 @@ static int res_split_check(int64_t planes, int H, int W) {
     return G2S_OK;
 }
 
+// the full-resolution operands are read and written as float2 (a NULL one counts as aligned)
+static bool aligned8(const void *a, const void *b = nullptr, const void *c = nullptr) {
+    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 7) == 0;
+}
+
 extern "C" int g2s_res_split_fwd(const float *x, float *relu_out, float *pool_out, int64_t planes, int H, int W,
                                  g2s_stream_t stream) {
     G2S_REQUIRE(x && relu_out && pool_out, "NULL pointer argument");
     int rc = res_split_check(planes, H, W);
     if (rc) return rc;
+    G2S_REQUIRE(aligned8(x, relu_out), "x and relu_out must be 8-byte aligned");
     const long windows = (long)planes * (H / 2) * (W / 2);
     res_split_fwd_kernel<<<cdiv(windows, 256), 256, 0, as_stream(stream)>>>(x, relu_out, pool_out, windows, H / 2, W / 2);
     return check_launch("g2s_res_split_fwd");
@@ -218,6 +224,7 @@ extern "C" int g2s_res_split_bwd(const float *x, const float *g_relu, const floa
     G2S_REQUIRE(x && gx && (g_relu || g_pool), "NULL pointer argument (one of g_relu / g_pool may be NULL)");
     int rc = res_split_check(planes, H, W);
     if (rc) return rc;
+    G2S_REQUIRE(aligned8(x, g_relu, gx), "x, g_relu and gx must be 8-byte aligned");
     const long windows = (long)planes * (H / 2) * (W / 2);
     res_split_bwd_kernel<<<cdiv(windows, 256), 256, 0, as_stream(stream)>>>(x, g_relu, g_pool, gx, windows, H / 2, W / 2);
     return check_launch("g2s_res_split_bwd");
@@ -229,6 +236,7 @@ extern "C" int g2s_avg_pyramid(const float *x, float *const *levels, int n_level
     const int S = 1 << n_levels;
     G2S_REQUIRE(H > 0 && W > 0 && H % S == 0 && W % S == 0, "H and W must be multiples of 2^n_levels");
     for (int l = 0; l < n_levels; l++) G2S_REQUIRE(levels[l], "NULL level pointer");
+    G2S_REQUIRE(aligned8(x), "x must be 8-byte aligned");
     float *o[4] = {levels[0], n_levels > 1 ? levels[1] : nullptr, n_levels > 2 ? levels[2] : nullptr,
                    n_levels > 3 ? levels[3] : nullptr};
     const long blocks = (long)planes * (H / S) * (W / S);

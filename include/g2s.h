@@ -343,13 +343,15 @@ int g2s_add_bias_scale(const float *a, const float *b, const float *bias, float 
 
 /* The mask pyramid of DiscriminatorLoss (GAN2Shape/losses.py:24-30): n_levels (1..4) successive
  * avg_pool2d(., 2, 2) of x [planes, H, W] in one launch; levels: HOST array of n_levels device pointers,
- * level l [planes, H / 2^(l+1), W / 2^(l+1)].  H, W multiples of 2^n_levels.  ATen's arithmetic per window. */
+ * level l [planes, H / 2^(l+1), W / 2^(l+1)].  H, W multiples of 2^n_levels.  ATen's arithmetic per window.
+ * x is read as float2: 8-byte aligned. */
 int g2s_avg_pyramid(const float *x, float *const *levels, int n_levels, int64_t planes, int H, int W,
                     g2s_stream_t stream);
 
 /* Entry of the offset encoder's residual block (GAN2Shape/networks.py:170-194): relu_out = relu(x) for the
  * residual path and pool_out = avg_pool2d(x, 2, 2) for the identity path in one pass over x [planes, H, W]
- * (H, W even); backward gx = g_relu * (x > 0) + g_pool / 4 in one pass (either gradient may be NULL). */
+ * (H, W even); backward gx = (x <= 0 ? 0 : g_relu) + g_pool / 4 in one pass (torch's rule: a NaN in x passes g_relu;
+ * either gradient may be NULL).  x, relu_out, g_relu and gx are accessed as float2: 8-byte aligned. */
 int g2s_res_split_fwd(const float *x, float *relu_out, float *pool_out, int64_t planes, int H, int W,
                       g2s_stream_t stream);
 int g2s_res_split_bwd(const float *x, const float *g_relu, const float *g_pool, float *gx, int64_t planes, int H,
