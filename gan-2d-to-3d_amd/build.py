@@ -53,6 +53,7 @@ SOURCES = {
     "mirror.hip": [],
     "canon_mask.hip": ["-ffp-contract=off"],     # restates its torch composition operation by operation
     "resample.hip": [],
+    "bank.hip": [],
     "probe.hip": [],
 }
 # The kernels take their descriptor struct by value.  Clang copies such a parameter into a private

@@ -42,6 +42,14 @@ class GraphedSteps:
         self._static_src = {}
         self._outputs = {}      # (kind, flip) -> (loss, collected): the static outputs of that captured graph
         self.warmup = warmup
+        # Hooks of the projected-sample bank (trainer._bank_hooks; all empty otherwise), each keyed by step kind and
+        # run eagerly on the current stream around EVERY iteration, warm-up or replay, never captured:
+        # before[kind](replay) in front of it, after[kind](collected) behind it; source[kind] replaces the previous kind's
+        # hand-off as what the iteration reads (static buffers that before[kind] fills).  With a before hook the CPU
+        # generator decides what the step sees, so the graphed loop then consumes it exactly as the eager loop does:
+        # `replay` tells the hook that the iteration's own Python (and the CPU draws in it) will not run, and a
+        # capture, which runs that Python once without being an iteration, leaves the generator where it was.
+        self.before, self.after, self.source = {}, {}, {}
         for opt in (trainer.optim_step1, trainer.optim_step2, trainer.optim_step3):
             for group in opt.param_groups:
                 if not group.get('capturable', False):
@@ -63,6 +71,8 @@ class GraphedSteps:
         return loss, collected
 
     def _source(self, kind):
+        if kind in self.source:
+            return self.source[kind]
         return {1: None, 2: self.collected[1], 3: self.collected[2]}[kind]
 
     def key(self, kind):
@@ -110,11 +120,18 @@ class GraphedSteps:
         with torch.cuda.stream(s):
             for _ in range(warmup):
                 optim.zero_grad(set_to_none=True)
+                if kind in self.before:
+                    self.before[kind](False)
                 warm_loss, warm_collected = self._iteration(kind, src)
+                if kind in self.after:
+                    self.after[kind](warm_collected)
         torch.cuda.current_stream().wait_stream(s)
         optim.zero_grad(set_to_none=True)
         key = self.key(kind)
+        cpu_rng = torch.get_rng_state() if kind in self.before else None
         self.graphs[key], loss, collected = self._record(kind, src)
+        if cpu_rng is not None:
+            torch.set_rng_state(cpu_rng)
         self._outputs[key] = (loss.detach(), collected)
         if not any(k[0] == kind for k in self._outputs if k != key):   # the first variant owns the hand-off buffers
             self.loss[kind], self.collected[kind] = self._outputs[key]
@@ -135,9 +152,16 @@ class GraphedSteps:
     def run(self, kind):
         """One training iteration of kind `kind` (graph replay)."""
         key = self.key(kind)
-        self.graphs[key].replay()
+        if kind in self.before:
+            self.before[kind](True)
+        self._replay(kind, key)
         self._publish(kind, *self._outputs[key])
+        if kind in self.after:
+            self.after[kind](self.collected[kind])
         return self.loss[kind]
+
+    def _replay(self, kind, key):
+        self.graphs[key].replay()
 
     def set_sample(self, image, latent, object_mask=None):
         self.image.copy_(image)
@@ -198,14 +222,11 @@ class GraphedJointSteps(GraphedSteps):
             self._update(kind)
         return (a, b), loss, collected
 
-    def run(self, kind):
-        key = self.key(kind)
+    def _replay(self, kind, key):
         a, b = self.graphs[key]
         a.replay()
         self.buckets[kind].all_reduce_mean()
         b.replay()
-        self._publish(kind, *self._outputs[key])
-        return self.loss[kind]
 
     def set_source(self, kind, collected):
         """Copy a hand-off into the static tensors the captured graph of step `kind` reads (the joint trainer

@@ -676,7 +676,24 @@ class GAN2Shape(nn.Module):
             # V and L see the image and its projected samples in ONE batch (1 + n), and so does LPIPS
             # below: the reference runs them as two calls each (model.py:113-131,243-250 and :159,275);
             # per-sample results are unchanged (no batch statistics in these nets), launches halve.
-            depth_raw, albedo1, view_all, light_all = self._run_nets(images, False, torch.cat([images, projected_samples], 0))
+            # A hand-off of the sample bank (bank.HandOff) carries that batch prebuilt: the gather wrote the image
+            # into row 0 of the buffer whose rows 1 .. are `projected_samples`, so the concatenation is already done.
+            # The contract of `batch` (checked as far as the host can see): [1 + b, 3, S, S] like the concatenation,
+            # its rows 1 .. ARE `projected_samples` (same memory), and row 0 holds `images` as it is now — the caller
+            # gathered with this image and has not changed it since; the values of row 0 are not compared here (that
+            # would be a device read-back per step).
+            prebuilt = getattr(collected, 'batch', None)
+            if prebuilt is not None and prebuilt.device != projected_samples.device:
+                prebuilt = None     # a hand-off gathered on another device was copied over above: nothing is prebuilt here
+            if prebuilt is not None:
+                if (tuple(prebuilt.shape) != (1 + b,) + tuple(images.shape[1:]) or prebuilt.dtype != images.dtype
+                        or not prebuilt.is_contiguous()
+                        or prebuilt[1:].data_ptr() != projected_samples.data_ptr()):
+                    raise ValueError(f"forward_step3: the hand-off's `batch` must be the contiguous [{1 + b}, "
+                                     f"{', '.join(str(v) for v in images.shape[1:])}] buffer [images; projected_samples] whose "
+                                     f"rows 1 .. are `projected_samples`; got {tuple(prebuilt.shape)} on {prebuilt.device}")
+            vl_batch = prebuilt if prebuilt is not None else torch.cat([images, projected_samples], 0)
+            depth_raw, albedo1, view_all, light_all = self._run_nets(images, False, vl_batch)
             # one split each (a single concatenation in backward) instead of two slices (a zero-fill
             # + copy each)
             view1, view = view_all.split([1, b])

@@ -60,6 +60,17 @@ class Trainer():
         # shorter than the stages repeats its last entry
         self.flip1_cfg = Trainer._flip_list(model_config.get('flip1_cfg'))
         self.flip3_cfg = Trainer._flip_list(model_config.get('flip3_cfg'))
+        # projected-sample bank (bank.py): `collect_iters` (absent or 0: off) step-2 iterations of every block are kept
+        # on the device and every step-3 iteration draws `step3_batch` of their samples; refused here if too large
+        self.collect_iters = int(model_config.get('collect_iters') or 0)
+        self.step3_batch = int(model_config.get('step3_batch') or self.n_proj_samples)
+        self.bank = None
+        if self.collect_iters > 0:
+            from .bank import DEFAULT_MAX_BYTES, SampleBank, check_bank_size
+            check_bank_size(self.collect_iters, self.n_proj_samples, self.image_size,
+                            int(model_config.get('bank_max_bytes', DEFAULT_MAX_BYTES)))
+            self.bank = SampleBank(self.collect_iters, self.n_proj_samples, self.image_size, self.device)
+        self._bank_left = 0
         prior_name = model_config.get('prior_name', 'ellipsoid')
         mask_accepts_batch = False
         want_parser_mask = self.object_mask and object_mask_fn is None
@@ -134,6 +145,34 @@ class Trainer():
         for name, cfg in (('flip1', self.flip1_cfg), ('flip3', self.flip3_cfg)):
             setattr(self.model, name, cfg[min(stage, len(cfg) - 1)] if cfg else False)
 
+    # ---- the projected-sample bank (None when `collect_iters` is off: every method below is then never reached)
+    def _bank_begin(self, n):
+        """A step-2 block of n iterations starts: the encoder has been re-trained since the last one, so what the
+        bank holds is stale."""
+        self.bank.reset()
+        self._bank_left = n
+
+    def _bank_collect(self, collected):
+        """After a step-2 iteration: keep its samples if it is one of the block's last `collect_iters`."""
+        self._bank_left -= 1
+        if self._bank_left < self.collect_iters:
+            self.bank.put(collected[0].detach(), collected[1].detach())
+
+    def _bank_draw(self, image):
+        """The hand-off of one step-3 iteration: `step3_batch` samples drawn from the bank (one randperm on the CPU
+        generator), gathered with the image in front."""
+        return self.bank.gather(self.bank.indices(self.step3_batch), image)
+
+    def _bank_hooks(self, graphed, image):
+        """Wire the bank into graphed steps: step 2's static outputs go into the bank after every iteration that
+        collects, and step 3 reads static hand-off buffers that a draw and one gather fill in front of every
+        iteration (graphs.GraphedSteps.after / before / source)."""
+        from .bank import StaticHandOff
+        static = StaticHandOff(self.bank, self.step3_batch, image)
+        graphed.after[2] = self._bank_collect
+        graphed.before[3] = static.fill
+        graphed.source[3] = static.handoff
+
     def fit(self, images_latents, plot_depth_map=False,
             stages=[{'step1': 1, 'step2': 1, 'step3': 1}] * 2, shuffle=False,
             rank=0, world_size=1, graphs=False, **_):
@@ -164,13 +203,19 @@ class Trainer():
                     optim = getattr(self, f'optim_step{step}')
                     forward = getattr(self.model, f'forward_step{step}')
                     collected, loss = None, None
+                    if self.bank is not None and step == 2:
+                        self._bank_begin(stages[stage]['step2'])
                     for _ in range(stages[stage][f'step{step}']):
                         optim.zero_grad()
+                        if self.bank is not None and step == 3 and len(self.bank) > 0:
+                            old_collected = self._bank_draw(image)
                         loss, collected = forward(image, latent, old_collected,
                                                   n_proj_samples=self.n_proj_samples, **mask_kw)
                         loss.backward()
                         optim.step()
                         zeropool.end()       # the step's cleared pool serves nothing beyond the step
+                        if self.bank is not None and step == 2:
+                            self._bank_collect(collected)
                         total_it += 1
                     self.history.append((data_index, stage, step,
                                          None if loss is None else float(loss.detach())))
@@ -198,6 +243,8 @@ class Trainer():
             masks = self.object_masks(image)    # eagerly, outside any capture
             if graphed is None:
                 graphed = GraphedSteps(self, image, latent, object_mask=masks)
+                if self.bank is not None:
+                    self._bank_hooks(graphed, graphed.image)
             else:
                 graphed.set_sample(image, latent, masks)   # graphs read the static image / latent / mask buffers
             for stage in range(len(stages)):
@@ -205,6 +252,8 @@ class Trainer():
                 for step in [1, 2, 3]:
                     n = stages[stage][f'step{step}']
                     done = 0
+                    if self.bank is not None and step == 2:
+                        self._bank_begin(n)
                     if n > 0 and not graphed.captured(step):
                         if step > 1 and graphed.collected[step - 1] is None:
                             raise RuntimeError(f"step {step} needs at least one step-{step - 1} iteration first")
@@ -337,11 +386,15 @@ class GeneralizingTrainer2(Trainer):
                             from .graphs import GraphedJointSteps
                             if graphed is None:
                                 graphed = GraphedJointSteps(self, image, latent, object_mask=mask_kw.get('object_mask'))
+                                if self.bank is not None:
+                                    self._bank_hooks(graphed, graphed.image)
                             else:
                                 graphed.set_sample(image, latent, mask_kw.get('object_mask'))
                             graphed.set_source(2, step1_collected)
                             n2, n3 = stages[0]['step2'], stages[0]['step3']
                             n3 = n3 if n2 > 0 else 0        # no step-2 hand-off, no step 3 (as in the eager loop below)
+                            if self.bank is not None:       # one bank serves all images: emptied for each
+                                self._bank_begin(n2)
                             for step, n in ((2, n2), (3, n3)):
                                 done = 0
                                 if n > 0 and not graphed.captured(step):     # warm-up iterations are real iterations
@@ -354,15 +407,21 @@ class GeneralizingTrainer2(Trainer):
                             self.history.append((index, epoch, 2, None if loss2 is None else float(loss2)))
                             self.history.append((index, epoch, 3, None if loss3 is None else float(loss3)))
                             continue
+                        if self.bank is not None:       # one bank serves all images: emptied for each
+                            self._bank_begin(stages[0]['step2'])
                         for _ in range(stages[0]['step2']):
                             self.optim_step2.zero_grad()
                             loss2, step2_collected = self.model.forward_step2(
                                 image, latent, step1_collected, n_proj_samples=self.n_proj_samples, **mask_kw)
                             loss2.backward()
                             self._sync_and_step(self.optim_step2)
+                            if self.bank is not None:
+                                self._bank_collect(step2_collected)
                             total_it += 1
                         for _ in range(stages[0]['step3'] if step2_collected is not None else 0):
                             self.optim_step3.zero_grad()
+                            if self.bank is not None:
+                                step2_collected = self._bank_draw(image)
                             loss3, _c = self.model.forward_step3(image, latent, step2_collected, **mask_kw)
                             loss3.backward()
                             self._sync_and_step(self.optim_step3)

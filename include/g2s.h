@@ -1134,6 +1134,26 @@ int g2s_resample_sep(const float *x, float *y, int planes, int Hin, int Win, int
                      const int *ylo, const int *ylen, const float *yw, int Ky,
                      const int *xlo, const int *xlen, const float *xw, int Kx, g2s_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Gather of the projected-sample bank (csrc/bank.hip; bank.py SampleBank.gather: the step-3 hand-off of the
+ * trainers with config `collect_iters` on).
+ *
+ * g2s_bank_gather: bank_img [rows, 3, S, S], bank_mask [rows, 1, S, S], idx [b] in DEVICE memory (int64 when idx64,
+ *   else int32), head [h, 3, S, S] (h >= 0; NULL exactly when h == 0)  ->
+ *     out_img  [h + b, 3, S, S]: rows 0 .. h are head, row h + j is bank_img[idx[j]]
+ *     out_mask [b, 1, S, S]:     row j is bank_mask[idx[j]]
+ *   in ONE launch; repeats in idx are allowed.  The launcher cannot look into idx: an entry outside 0 .. rows - 1 is
+ *   clamped into the range by the kernel (nothing is read out of bounds, every output element is still written) and
+ *   j + 1, the 1-based position of one such entry, is stored to *err (DEVICE int32; the caller clears it and reads
+ *   it when it wants the report).  Because idx is read on the device, the launch can be captured, or run in front
+ *   of a replayed graph, with a static index buffer.
+ *   16-byte accesses for a copy whose row length is a multiple of 4 floats and whose base addresses are all 16-byte
+ *   aligned (chosen separately for the image rows with the head and for the mask rows), dword accesses otherwise.
+ *   Exact copies: no arithmetic, no atomics, no workspace.  The outputs must not overlap the inputs.
+ * ---------------------------------------------------------------------------------------- */
+int g2s_bank_gather(const float *bank_img, const float *bank_mask, long rows, const void *idx, int idx64, int b,
+                    const float *head, int h, float *out_img, float *out_mask, int S, int *err, g2s_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
