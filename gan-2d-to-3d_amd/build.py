@@ -54,6 +54,7 @@ SOURCES = {
     "canon_mask.hip": ["-ffp-contract=off"],     # restates its torch composition operation by operation
     "resample.hip": [],
     "bank.hip": [],
+    "mvn.hip": [],
     "probe.hip": [],
 }
 # The kernels take their descriptor struct by value.  Clang copies such a parameter into a private

@@ -591,6 +591,19 @@ class GAN2Shape(nn.Module):
         mask = mask[:, 0, None, ...]
         return pseudo_im.clamp(min=-1, max=1), mask.contiguous()
 
+    # ------------------------------------------------------------------ the priors' raw material
+    def estimate_view_light(self, images):
+        """The raw view (B,6) and light (B,4) parameters of `images` (B,3,S,S), any B, under no_grad: exactly
+        viewpoint_net(images) + view mean and lighting_net(images) + light mean, as forward_step1 forms them
+        (model.py:110-133) — no view_scale, no get_view_transformation.  The V and L nets go through the paired route
+        when paired_nets is on, as in the steps.  What view_light.fit_view_light fits the priors to."""
+        with torch.no_grad():
+            if self.paired_nets:
+                view, light = networks.forward_pair(self.viewpoint_net, self.lighting_net, images)
+            else:
+                view, light = self.viewpoint_net(images), self.lighting_net(images)
+            return self._add_means(view, light)
+
     # ------------------------------------------------------------------ manipulation through the GAN
     def decompose(self, image, object_mask=None):
         """The head of forward_step1 without its losses, under no_grad: the four nets on `image` (1,3,S,S) ->

@@ -1154,6 +1154,31 @@ int g2s_resample_sep(const float *x, float *y, int planes, int Hin, int Win, int
 int g2s_bank_gather(const float *bank_img, const float *bank_mask, long rows, const void *idx, int idx64, int b,
                     const float *head, int h, float *out_img, float *out_mask, int S, int *err, g2s_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mean, covariance and block Cholesky factor of a set of rows (csrc/mvn.hip; view_light.py mvn_fit: the fit of the
+ * view and light priors, view_mvn.pth / light_mvn.pth, from a trained model's estimates).
+ *
+ * g2s_mvn_fit: rows [N, D] fp32 with row stride ld >= D (in floats; columns D .. ld - 1 are never read),
+ *   1 <= D <= G2S_MVN_MAX_D, 2 <= N < 2^31; blocks [nblk] HOST ints, 1 <= nblk <= G2S_MVN_MAX_BLOCKS, each >= 1,
+ *   summing to D  ->
+ *     mean [D]       fp32
+ *     cov  [D, D]    fp32, the full joint covariance with divisor N - 1 (numpy.cov / torch.cov) plus ridge on the
+ *                    diagonal; exactly symmetric (the upper triangle is computed and mirrored)
+ *     tril [D, D]    fp32, block diagonal: diagonal block k holds the lower Cholesky factor of that block of cov;
+ *                    every other entry, the upper triangles included, is 0.0
+ *     status         DEVICE int32: 0 fine; 1 + j: the pivot of global column j was not positive (tril is then
+ *                    unspecified, mean and cov are valid); -1: some input was not finite (mean, cov, tril unspecified)
+ *   in ONE launch of ONE workgroup of 256 threads.  Two passes: the mean is accumulated in double, then the centred
+ *   products in double; the Cholesky runs in double on the double covariance; each output is rounded to fp32 once.
+ *   Thread t takes rows t, t + 256, ... in ascending order and the partials meet in a fixed tree in LDS: no atomics,
+ *   no workspace, bit-identical from run to run whatever g2s_set_deterministic says.  The outputs must not overlap
+ *   rows.  Every check precedes the launch.
+ * ---------------------------------------------------------------------------------------- */
+#define G2S_MVN_MAX_D 16
+#define G2S_MVN_MAX_BLOCKS 4
+int g2s_mvn_fit(const float *rows, long N, int D, long ld, const int *blocks, int nblk, double ridge,
+                float *mean, float *cov, float *tril, int *status, g2s_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
