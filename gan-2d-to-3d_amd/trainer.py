@@ -5,7 +5,8 @@ in the reference's main.py:130-153: per image, optional prior pre-training of th
 stages x steps {1,2,3} x N iterations of zero_grad / forward_stepK / backward / Adam.step, with the
 last `collected` of step K handed to step K+1.  Three persistent Adam optimisers over {A}, {E},
 {L,V,D,A} (lr 1e-4, classic L2 weight decay 5e-4), a fresh Adam for every image's prior
-pre-training (trainer.py:40-48,131,163-171).
+pre-training (trainer.py:40-48,131,163-171).  The iteration itself is stated once, in graphs.EagerSteps; both
+trainers run every per-image block of it through a runner's `run_block(kind, n)`, eagerly or as replayed HIP graphs.
 
 Added (not in the reference): `rank` / `world_size` image sharding — rank r trains images
 r, r+W, r+2W, ... with no collective (the per-image optimisation is independent; note that nets
@@ -19,6 +20,7 @@ import torch
 from torch.utils.data import DataLoader, Subset
 
 from . import zeropool
+from .graphs import EagerJointSteps, EagerSteps, GraphedJointSteps, GraphedSteps
 from .priors import PriorGenerator
 from .sharding import shard_indices  # noqa: F401  (re-exported)
 
@@ -163,109 +165,64 @@ class Trainer():
         generator), gathered with the image in front."""
         return self.bank.gather(self.bank.indices(self.step3_batch), image)
 
-    def _bank_hooks(self, graphed, image):
-        """Wire the bank into graphed steps: step 2's static outputs go into the bank after every iteration that
-        collects, and step 3 reads static hand-off buffers that a draw and one gather fill in front of every
-        iteration (graphs.GraphedSteps.after / before / source)."""
-        from .bank import StaticHandOff
-        static = StaticHandOff(self.bank, self.step3_batch, image)
-        graphed.after[2] = self._bank_collect
-        graphed.before[3] = static.fill
-        graphed.source[3] = static.handoff
+    def _bank_hooks(self, steps):
+        """Wire the bank into a runner (graphs.EagerSteps.after / before / source): step 2's hand-off goes into the bank
+        after every iteration that collects, and in front of every step-3 iteration a draw and one gather make what it
+        reads — a fresh hand-off for an eager runner (all rows of a bank that holds fewer than `step3_batch`; nothing
+        of an empty one), the fill of static buffers for a graphed one."""
+        steps.after[2] = self._bank_collect
+        if isinstance(steps, GraphedSteps):
+            from .bank import StaticHandOff
+            static = StaticHandOff(self.bank, self.step3_batch, steps.image)
+            steps.before[3] = static.fill
+            steps.source[3] = static.handoff
+        else:
+            def draw(replay):
+                steps.source[3] = self._bank_draw(steps.image) if len(self.bank) > 0 else None
+            steps.before[3] = draw
 
     def fit(self, images_latents, plot_depth_map=False,
             stages=[{'step1': 1, 'step2': 1, 'step3': 1}] * 2, shuffle=False,
             rank=0, world_size=1, graphs=False, **_):
         """graphs=True replays each step kind as a HIP graph (graphs.py): same iterations, same
         order; needs Trainer(..., capturable=True) and a non-default current stream."""
-        if graphs:
-            return self._fit_graphed(images_latents, stages, shuffle, rank, world_size)
+        if graphs and not self.capturable:
+            raise RuntimeError("graphs=True needs Trainer(..., capturable=True)")
         total_it = 0
-        n_stages = len(stages)
         data = images_latents
         if world_size > 1:
             data = Subset(images_latents, shard_indices(len(images_latents), rank, world_size))
         # the original training is instance-based => batch size = 1
         dataloader = DataLoader(data, batch_size=1, shuffle=shuffle, num_workers=self.n_workers)
-        for batch in dataloader:
-            image, latent, data_index = batch
+        steps = None
+        for image, latent, data_index in dataloader:
             image, latent = image.to(self.device), latent.to(self.device)
             data_index = int(data_index[0])
             logging.info(f'Training on image {data_index}')
             if not self.debug and self.load_dict is None:
                 self.pretrain_on_prior(image, data_index, plot_depth_map)
-            mask_kw = self._mask_kwargs(self.object_masks(image))       # once per image
-            stage = 0
-            for stage in range(n_stages):
-                old_collected = None
-                self._set_flips(stage)
+            masks = self.object_masks(image)       # once per image, eagerly: outside any capture
+            if steps is None:
+                steps = (GraphedSteps if graphs else EagerSteps)(self, image, latent, object_mask=masks)
+                if self.bank is not None:
+                    self._bank_hooks(steps)
+            else:
+                steps.set_sample(image, latent, masks)   # graphs read the static image / latent / mask buffers
+            stage = -1 if graphs else 0     # the stage an empty schedule's checkpoint is named after
+            for stage in range(len(stages)):
+                self._set_flips(stage)      # a captured step depends on its flip switch: graphs are keyed by (kind, flip)
+                if not graphs:      # an eager hand-off does not outlive its stage; a graph keeps reading its static buffers
+                    steps.collected = {1: None, 2: None, 3: None}
                 for step in [1, 2, 3]:
-                    optim = getattr(self, f'optim_step{step}')
-                    forward = getattr(self.model, f'forward_step{step}')
-                    collected, loss = None, None
+                    n = stages[stage][f'step{step}']
                     if self.bank is not None and step == 2:
-                        self._bank_begin(stages[stage]['step2'])
-                    for _ in range(stages[stage][f'step{step}']):
-                        optim.zero_grad()
-                        if self.bank is not None and step == 3 and len(self.bank) > 0:
-                            old_collected = self._bank_draw(image)
-                        loss, collected = forward(image, latent, old_collected,
-                                                  n_proj_samples=self.n_proj_samples, **mask_kw)
-                        loss.backward()
-                        optim.step()
-                        zeropool.end()       # the step's cleared pool serves nothing beyond the step
-                        if self.bank is not None and step == 2:
-                            self._bank_collect(collected)
-                        total_it += 1
-                    self.history.append((data_index, stage, step,
-                                         None if loss is None else float(loss.detach())))
-                    old_collected = collected
+                        self._bank_begin(n)
+                    total_it += steps.run_block(step, n)
+                    if n > 0 or not graphs:     # the eager loop keeps a row for an empty block
+                        self.history.append((data_index, stage, step, float(steps.loss[step]) if n > 0 else None))
             if self.save_ckpts:
                 self.model.save_checkpoint(data_index, stage, total_it, self.category)
         logging.info('Finished Training')
-        return total_it
-
-    def _fit_graphed(self, images_latents, stages, shuffle, rank, world_size):
-        from .graphs import GraphedSteps
-        if not self.capturable:
-            raise RuntimeError("graphs=True needs Trainer(..., capturable=True)")
-        data = images_latents
-        if world_size > 1:
-            data = Subset(images_latents, shard_indices(len(images_latents), rank, world_size))
-        dataloader = DataLoader(data, batch_size=1, shuffle=shuffle, num_workers=self.n_workers)
-        total_it = 0
-        graphed = None
-        for image, latent, data_index in dataloader:
-            image, latent = image.to(self.device), latent.to(self.device)
-            data_index = int(data_index[0])
-            if not self.debug and self.load_dict is None:
-                self.pretrain_on_prior(image, data_index)
-            masks = self.object_masks(image)    # eagerly, outside any capture
-            if graphed is None:
-                graphed = GraphedSteps(self, image, latent, object_mask=masks)
-                if self.bank is not None:
-                    self._bank_hooks(graphed, graphed.image)
-            else:
-                graphed.set_sample(image, latent, masks)   # graphs read the static image / latent / mask buffers
-            for stage in range(len(stages)):
-                self._set_flips(stage)      # a captured step depends on its flip switch: graphs are keyed by (kind, flip)
-                for step in [1, 2, 3]:
-                    n = stages[stage][f'step{step}']
-                    done = 0
-                    if self.bank is not None and step == 2:
-                        self._bank_begin(n)
-                    if n > 0 and not graphed.captured(step):
-                        if step > 1 and graphed.collected[step - 1] is None:
-                            raise RuntimeError(f"step {step} needs at least one step-{step - 1} iteration first")
-                        # the warm-up iterations are real iterations: never more than requested
-                        done = graphed.capture(step, warmup=min(graphed.warmup, n))
-                    for _ in range(n - done):
-                        graphed.run(step)
-                    total_it += n
-                    if n > 0:
-                        self.history.append((data_index, stage, step, float(graphed.loss[step])))
-            if self.save_ckpts:
-                self.model.save_checkpoint(data_index, len(stages) - 1, total_it, self.category)
         return total_it
 
     def pretrain_on_prior(self, image, i_batch, plot_depth_map=False):
@@ -342,13 +299,14 @@ class GeneralizingTrainer2(Trainer):
             rank=0, world_size=1, graphs=False, **_):
         """graphs=True: the per-image steps 2 / 3 replay as HIP graphs in two segments with the gradient
         all-reduce between them (graphs.GraphedJointSteps; needs capturable=True and a non-default current
-        stream); the batched step 1 stays eager (ragged batches, and under W > 1 a collective in its forward)."""
+        stream), graphs=False runs the same blocks through graphs.EagerJointSteps; the batched step 1 stays eager
+        (ragged batches, and under W > 1 a collective in its forward)."""
         from . import sharding
         # centre of the depth over the WHOLE image batch (all ranks) — only where the reference
         # itself runs a batch of images through the depth net: prior pre-training and step 1
         whole_batch = sharding.global_mean if world_size > 1 else None
         total_it = 0
-        graphed = None
+        steps = None
         if graphs and not self.capturable:
             raise RuntimeError("graphs=True needs GeneralizingTrainer2(..., capturable=True)")
         self._set_flips(0)      # entry 0 of flip1_cfg / flip3_cfg, as stages[0] below
@@ -377,57 +335,26 @@ class GeneralizingTrainer2(Trainer):
                         canon_masks = [canon_masks]
                     for bi, index in enumerate(indices):
                         image, latent = images[bi:bi + 1], latents[bi:bi + 1]
-                        mask_kw = self._mask_kwargs(None if masks is None else masks[bi:bi + 1])    # this sample's mask
+                        mask = None if masks is None else masks[bi:bi + 1]      # this sample's mask
                         step1_collected = (normals[bi:bi + 1].detach(), lights_a[bi:bi + 1].detach(),
                                            lights_b[bi:bi + 1].detach(), albedos[bi:bi + 1].detach(),
                                            depths[bi:bi + 1].detach(), canon_masks[bi])
-                        loss2 = loss3 = step2_collected = None
-                        if graphs:
-                            from .graphs import GraphedJointSteps
-                            if graphed is None:
-                                graphed = GraphedJointSteps(self, image, latent, object_mask=mask_kw.get('object_mask'))
-                                if self.bank is not None:
-                                    self._bank_hooks(graphed, graphed.image)
-                            else:
-                                graphed.set_sample(image, latent, mask_kw.get('object_mask'))
-                            graphed.set_source(2, step1_collected)
-                            n2, n3 = stages[0]['step2'], stages[0]['step3']
-                            n3 = n3 if n2 > 0 else 0        # no step-2 hand-off, no step 3 (as in the eager loop below)
-                            if self.bank is not None:       # one bank serves all images: emptied for each
-                                self._bank_begin(n2)
-                            for step, n in ((2, n2), (3, n3)):
-                                done = 0
-                                if n > 0 and not graphed.captured(step):     # warm-up iterations are real iterations
-                                    done = graphed.capture(step, warmup=min(graphed.warmup, n))
-                                for _ in range(n - done):
-                                    graphed.run(step)
-                                total_it += n
-                            loss2 = graphed.loss.get(2) if n2 > 0 else None
-                            loss3 = graphed.loss.get(3) if n3 > 0 else None
-                            self.history.append((index, epoch, 2, None if loss2 is None else float(loss2)))
-                            self.history.append((index, epoch, 3, None if loss3 is None else float(loss3)))
-                            continue
-                        if self.bank is not None:       # one bank serves all images: emptied for each
-                            self._bank_begin(stages[0]['step2'])
-                        for _ in range(stages[0]['step2']):
-                            self.optim_step2.zero_grad()
-                            loss2, step2_collected = self.model.forward_step2(
-                                image, latent, step1_collected, n_proj_samples=self.n_proj_samples, **mask_kw)
-                            loss2.backward()
-                            self._sync_and_step(self.optim_step2)
+                        if steps is None:
+                            steps = (GraphedJointSteps if graphs else EagerJointSteps)(self, image, latent, object_mask=mask)
                             if self.bank is not None:
-                                self._bank_collect(step2_collected)
-                            total_it += 1
-                        for _ in range(stages[0]['step3'] if step2_collected is not None else 0):
-                            self.optim_step3.zero_grad()
-                            if self.bank is not None:
-                                step2_collected = self._bank_draw(image)
-                            loss3, _c = self.model.forward_step3(image, latent, step2_collected, **mask_kw)
-                            loss3.backward()
-                            self._sync_and_step(self.optim_step3)
-                            total_it += 1
-                        self.history.append((index, epoch, 2, None if loss2 is None else float(loss2.detach())))
-                        self.history.append((index, epoch, 3, None if loss3 is None else float(loss3.detach())))
+                                self._bank_hooks(steps)
+                        else:
+                            steps.set_sample(image, latent, mask)
+                        steps.set_source(2, step1_collected)
+                        n2 = stages[0]['step2']
+                        n3 = stages[0]['step3'] if n2 > 0 else 0        # no step-2 hand-off, no step 3
+                        for step, n in ((2, n2), (3, n3)):
+                            if self.bank is not None and step == 2:     # one bank serves all images: emptied for each
+                                self._bank_begin(n)
+                            total_it += steps.run_block(step, n)
+                        # both rows always, read back (a synchronisation) once both blocks are queued
+                        self.history += [(index, epoch, step, float(steps.loss[step]) if n > 0 else None)
+                                         for step, n in ((2, n2), (3, n3))]
                 if epoch % 20 == 0 and self.save_ckpts and rank == 0:
                     self.model.save_checkpoint("", epoch, total_it, self.category)
         finally:
