@@ -42,6 +42,7 @@ SOURCES = {
     "grid_sample.hip": ["-ffp-contract=off"],
     "priors.hip": ["-ffp-contract=off"],         # restates the torch expressions of priors.py operation by operation
     "metrics.hip": ["-ffp-contract=off"],        # as geometry.hip (shared normals); var = E[d^2] - E[d]^2 is exactly 0 for one pixel
+    "image_metrics.hip": ["-ffp-contract=off"],  # a == b: numerator and denominator of SSIM are the same bits
     "parsing.hip": [],
     "groupnorm.hip": [],
     "conv_wgrad.hip": [],

@@ -3,7 +3,7 @@ its plotting.
 
     python -m gan2shape_amd.evaluate --config configs/face.yml --ckpt <file> --out results/eval
                                      [--images 0 3 7] [--mask] [--gt-depth <dir> [--gt-background]]
-                                     [--record-loss <name>]
+                                     [--record-loss <name>] [--recon-metrics]
 
 For every image: `model.evaluate_results` (or `evaluate_results_masked` with --mask, NaN outside the object
 mask of MaskingModel), optionally the step-1 loss (evaluate_results.py:92-94,107-114).  Images go through the
@@ -14,8 +14,16 @@ batched `metrics.depth_metrics` call at the end.
 Written: <out>/depth/<stem>.npy (float32 (H, W)), <out>/metrics.json ({"images": {stem: {count, mae, mse, side,
 mad}}, "summary": DepthMetrics.summary()}; with no --gt-depth only the names), <out>/step1_<name>_model.npy.
 
---config is one yml file (the reference merges minimal_config.yml with configs/<category>.yml on its command line;
-that merge stays out of scope).  Keys read here: image_size, root_path + category (the dataset is
+--recon-metrics scores what needs no ground truth: the reconstruction `recon_im` that `evaluate_results` renders from
+the recovered depth, albedo, view and light, against the input image — `metrics.image_metrics` (MAE, MSE, PSNR, SSIM),
+ONE batched call over all images at the end, inside the MaskingModel mask (the finite pixels of the masked depth) with
+--mask.  data_range is 2: dataset.ImageDataset hands out images in [-1, 1] and the model's reconstruction is clamped
+to [-1, 1] (model.py, `grid_sample(texture, ..., -1, 1)`).  Per image the six values go to images[stem]["recon"], their
+`ImageMetrics.summary()` to "recon_summary"; a model with a `perceptual_loss` module (the LPIPS of step 1) also gets
+images[stem]["recon"]["lpips"].  Without the flag nothing of this is computed, written or logged.
+
+--config is one yml file (`reconstruct` merges minimal_config.yml with configs/<category>.yml as the reference's
+command line does; `config.load_config` reads either form).  Keys read here: image_size, root_path + category (the dataset is
 <root_path>/<category>/list.txt), parsing_ckpt_dir / parsing_size (--mask), and everything GAN2Shape reads.
 --ckpt is the checkpoint file of any one net (`<net>_image_..._stage_..._it_....pth`); the other four are
 found beside it under their own names, as `load_from_checkpoint` expects.  --gt-depth holds <image stem>.npy:
@@ -30,7 +38,9 @@ import os
 import numpy as np
 import torch
 
-from .metrics import KEYS, DepthMetrics, depth_metrics, gt_mask_from_depth
+from .metrics import IMAGE_KEYS, KEYS, DepthMetrics, ImageMetrics, depth_metrics, gt_mask_from_depth, image_metrics
+
+IMAGE_DATA_RANGE = 2.0      # images and reconstructions live in [-1, 1]
 
 
 def checkpoint_path_of(ckpt):
@@ -52,25 +62,55 @@ def _json_number(v):
     return v if np.isfinite(v) else None
 
 
+def summary_json(summary):
+    """A `summary()` dict of metrics.DepthMetrics / ImageMetrics with its (mean, std) tuples as JSON lists."""
+    return {k: [_json_number(x) for x in v] if isinstance(v, tuple) else v for k, v in summary.items()}
+
+
+def recon_scores(recons, images, masks=None, perceptual=None):
+    """One `image_metrics` call over all reconstructions (N, 3, H, W) against their images -> (per-image list of
+    {count, mae, mse, psnr, ssim_count, ssim[, lpips]} with JSON numbers, ImageMetrics.summary()).  perceptual: the
+    model's LPIPS module or None; it runs image by image, as in step 1."""
+    scores = image_metrics(recons, images, masks, data_range=IMAGE_DATA_RANGE)
+    acc = ImageMetrics()
+    acc.update(scores)
+    host = {k: scores[k].cpu().numpy().astype(np.float64) for k in IMAGE_KEYS}
+    rows = [{k: _json_number(host[k][j]) for k in IMAGE_KEYS} for j in range(len(recons))]
+    if perceptual is not None:
+        with torch.no_grad():
+            for j, row in enumerate(rows):
+                row["lpips"] = _json_number(perceptual(recons[j:j + 1], images[j:j + 1]).mean())
+    return rows, acc.summary()
+
+
+def log_recon_summary(s, log):
+    log(f"{s['images']} reconstructions scored, {s['skipped']} skipped (no counted pixel), {s['exact']} exact")
+    for k in ("mae", "mse", "psnr", "ssim"):
+        log(f"  {k:5s} {s[k][0]:.6g} +- {s[k][1]:.6g}")
+
+
 def _stems(dataset):
     return [os.path.splitext(os.path.basename(name))[0] for name in dataset.file_list]
 
 
 def evaluate(model, dataset, out_dir, masking_model=None, gt_depth_dir=None, gt_background=False, record_loss=None,
-             device=None, log=print):
+             device=None, log=print, recon_metrics=False):
     """The loop of evaluate_results.py:88-114 over `dataset` (an ImageDataset).  Returns the dict written to
-    metrics.json."""
+    metrics.json.  recon_metrics: also score each reconstruction against its image (module docstring)."""
     device = torch.device(device if device is not None else model.device)
     stems = _stems(dataset)
     os.makedirs(os.path.join(out_dir, "depth"), exist_ok=True)
-    depths, losses = [], []
+    depths, losses, recons, images = [], [], [], []
     for i in range(len(dataset)):
         image = dataset[i].unsqueeze(0).to(device)
         if masking_model is not None:
-            _recon_im, depth = model.evaluate_results_masked(image, masking_model)
+            recon_im, depth = model.evaluate_results_masked(image, masking_model)
         else:
-            _recon_im, depth = model.evaluate_results(image)
+            recon_im, depth = model.evaluate_results(image)
         depths.append(depth.detach().reshape(depth.shape[-2], depth.shape[-1]).float())
+        if recon_metrics:
+            recons.append(recon_im.detach()[0].float())
+            images.append(image[0].float())
         if record_loss is not None:
             loss, _ = model.forward_step1(image, None, None, step1=True, eval=False)
             losses.append(float(loss.detach().cpu()))
@@ -94,10 +134,17 @@ def evaluate(model, dataset, out_dir, masking_model=None, gt_depth_dir=None, gt_
         for j, stem in enumerate(stems):
             result["images"][stem] = {k: _json_number(host[k][j]) for k in KEYS}
         s = acc.summary()
-        result["summary"] = {k: [_json_number(x) for x in v] if isinstance(v, tuple) else v for k, v in s.items()}
+        result["summary"] = summary_json(s)
         log(f"{s['images']} images scored, {s['skipped']} skipped (no counted pixel)")
         for k in ("mae", "mse", "side", "mad"):
             log(f"  {k:5s} {s[k][0]:.6g} +- {s[k][1]:.6g}")
+    if recon_metrics and recons:
+        masks = torch.isfinite(depths).float() if masking_model is not None else None
+        rows, s = recon_scores(torch.stack(recons), torch.stack(images), masks, getattr(model, "perceptual_loss", None))
+        for stem, row in zip(stems, rows):
+            result["images"][stem]["recon"] = row
+        result["recon_summary"] = summary_json(s)
+        log_recon_summary(s, log)
     if record_loss is not None:
         losses = np.array(losses)
         log(f"mean =  {np.mean(losses) if len(losses) else float('nan')}")
@@ -124,6 +171,8 @@ def build_parser():
                         help="the farthest value of each ground-truth map is background (BFM convention)")
     parser.add_argument("--record-loss", dest="record_loss", default=None,
                         help="name: record the step-1 loss per image, save <out>/step1_<name>_model.npy")
+    parser.add_argument("--recon-metrics", dest="recon_metrics", action="store_true",
+                        help="score each reconstruction against its image: MAE, MSE, PSNR, SSIM (inside the mask with --mask)")
     parser.add_argument("--out", required=True, help="output directory")
     parser.add_argument("--device", default="cuda")
     return parser
@@ -150,7 +199,8 @@ def main(argv=None, model=None, masking_model=None):
     dataset = ImageDataset(os.path.join(config["root_path"], category), subset=args.images,
                            transform=default_transform(config["image_size"], config.get("crop"), config.get("origin_size")))
     return evaluate(model, dataset, args.out, masking_model=masking_model if args.mask else None,
-                    gt_depth_dir=args.gt_depth, gt_background=args.gt_background, record_loss=args.record_loss, device=device)
+                    gt_depth_dir=args.gt_depth, gt_background=args.gt_background, record_loss=args.record_loss, device=device,
+                    recon_metrics=args.recon_metrics)
 
 
 if __name__ == "__main__":

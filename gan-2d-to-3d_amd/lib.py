@@ -129,6 +129,8 @@ SIGNATURES = {
     "g2s_parse_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, C.c_uint32, _p, _p, _p, _p, _sz, _p]),
     "g2s_depth_metrics_workspace_bytes": (_sz, [_i, _i, _i]),
     "g2s_depth_metrics": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _sz, _p]),
+    "g2s_image_metrics_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "g2s_image_metrics": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _p, _p, _sz, _p]),
     "g2s_ada_up2": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "g2s_ada_up2_bwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "g2s_ada_warp_down": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),

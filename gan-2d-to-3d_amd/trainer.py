@@ -183,9 +183,10 @@ class Trainer():
 
     def fit(self, images_latents, plot_depth_map=False,
             stages=[{'step1': 1, 'step2': 1, 'step3': 1}] * 2, shuffle=False,
-            rank=0, world_size=1, graphs=False, **_):
+            rank=0, world_size=1, graphs=False, on_image_done=None, **_):
         """graphs=True replays each step kind as a HIP graph (graphs.py): same iterations, same
-        order; needs Trainer(..., capturable=True) and a non-default current stream."""
+        order; needs Trainer(..., capturable=True) and a non-default current stream.
+        on_image_done(data_index, image, trainer): called after the last stage of each image, before its checkpoint."""
         if graphs and not self.capturable:
             raise RuntimeError("graphs=True needs Trainer(..., capturable=True)")
         total_it = 0
@@ -220,6 +221,8 @@ class Trainer():
                     total_it += steps.run_block(step, n)
                     if n > 0 or not graphs:     # the eager loop keeps a row for an empty block
                         self.history.append((data_index, stage, step, float(steps.loss[step]) if n > 0 else None))
+            if on_image_done is not None:
+                on_image_done(data_index, image, self)
             if self.save_ckpts:
                 self.model.save_checkpoint(data_index, stage, total_it, self.category)
         logging.info('Finished Training')
@@ -296,11 +299,13 @@ class GeneralizingTrainer2(Trainer):
 
     def fit(self, images_latents, plot_depth_map=False,
             stages=[{'step1': 1, 'step2': 1, 'step3': 1}] * 2, batch_size=2, shuffle=False,
-            rank=0, world_size=1, graphs=False, **_):
+            rank=0, world_size=1, graphs=False, on_image_done=None, **_):
         """graphs=True: the per-image steps 2 / 3 replay as HIP graphs in two segments with the gradient
         all-reduce between them (graphs.GraphedJointSteps; needs capturable=True and a non-default current
         stream), graphs=False runs the same blocks through graphs.EagerJointSteps; the batched step 1 stays eager
-        (ragged batches, and under W > 1 a collective in its forward)."""
+        (ragged batches, and under W > 1 a collective in its forward).
+        on_image_done(data_index, image, trainer): called once per image of this rank, in dataset order, after the
+        last epoch (the model is shared: only then is an image's result final)."""
         from . import sharding
         # centre of the depth over the WHOLE image batch (all ranks) — only where the reference
         # itself runs a batch of images through the depth net: prior pre-training and step 1
@@ -357,6 +362,11 @@ class GeneralizingTrainer2(Trainer):
                                          for step, n in ((2, n2), (3, n3))]
                 if epoch % 20 == 0 and self.save_ckpts and rank == 0:
                     self.model.save_checkpoint("", epoch, total_it, self.category)
+            if on_image_done is not None:      # read straight from the dataset: a DataLoader would draw a seed
+                for k in range(len(images_latents)):
+                    image, _latent, index = images_latents[k]
+                    if world_size == 1 or (int(index) % batch_size) % world_size == rank % world_size:
+                        on_image_done(int(index), image.unsqueeze(0).to(self.device), self)
         finally:
             self.model.batch_mean = None
         logging.info('Finished Training')

@@ -946,6 +946,34 @@ int g2s_depth_metrics(const float *depth_pred, const float *depth_gt, const floa
                       const float *rays, int B, int H, int W, int erode, float *out, void *workspace,
                       size_t workspace_bytes, g2s_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * How well an image a reproduces an image b (csrc/image_metrics.hip): masked MAE, MSE, PSNR and the mean structural
+ * similarity (SSIM; Wang, Bovik, Sheikh, Simoncelli 2004), per image, in two launches.
+ * a, b [B, C, H, W] f32, finite; mask [B, H, W] f32 or NULL (all ones); out [B, 6] = {count, mae, mse, psnr,
+ * ssim_count, ssim} of image b.  L = data_range > 0, the width of the images' value range.
+ *   count          number n of pixels with mask > 0.5 (pixels, not pixels x channels; exact to 2^24)
+ *   mae, mse       d = a - b;  mae = sum |d| / (n C),  mse = sum d^2 / (n C), over the counted pixels and all channels
+ *   psnr           10 log10(L^2 / mse); +inf when mse == 0
+ *   window         w[j] = exp(-(j - 5)^2 / (2 1.5^2)) / sum_j of the same, j = 0 .. 10: 11 taps, sigma 1.5, sum 1.
+ *                  F(u)(y, x) = sum_i sum_j w[i] w[j] u(y - 5 + i, x - 5 + j), defined only where the whole 11 x 11
+ *                  window lies inside the image: centres (y, x) in [5, H - 6] x [5, W - 6].  No padding.
+ *   SSIM map       per channel:  mu_a = F(a), mu_b = F(b);  var_a = F(a a) - mu_a mu_a,  var_b = F(b b) - mu_b mu_b,
+ *                  cov = F(a b) - mu_a mu_b  (weighted, biased moments);  C1 = (0.01 L)^2,  C2 = (0.03 L)^2;
+ *                  S = ((2 mu_a mu_b + C1) (2 cov + C2)) / ((mu_a mu_a + mu_b mu_b + C1) (var_a + var_b + C2))
+ *   ssim_count     number n_w of window centres with mask > 0.5 at the centre
+ *   ssim           sum of S over the counted centres and all channels / (n_w C).  For a == b it is exactly 1.
+ *   empty          n == 0: count 0 and mae, mse, psnr NaN.  H < 11, W < 11 or n_w == 0: ssim_count 0, ssim NaN.
+ * Without a mask this is skimage.metrics.structural_similarity(gaussian_weights=True, sigma=1.5,
+ * use_sample_covariance=False, data_range=L) averaged over the channels.  The filter and all sums run in double.
+ * 1 <= C <= 4, 1 <= H, W <= 32768, 1 <= B <= 65535.  workspace: >= g2s_image_metrics_workspace_bytes(B, C, H, W)
+ * bytes, 8-byte aligned, scratch of one call; NULL / short is G2S_ERR_WORKSPACE.  Every check precedes the first
+ * launch; nothing allocates or synchronises; no atomics: every sum has one fixed order, the output is bit-identical
+ * from run to run and in either mode of g2s_set_deterministic; the two launches can be captured in a graph.
+ * ---------------------------------------------------------------------------------------- */
+size_t g2s_image_metrics_workspace_bytes(int B, int C, int H, int W);
+int g2s_image_metrics(const float *a, const float *b, const float *mask, int B, int C, int H, int W, float data_range,
+                      float *out, void *workspace, size_t workspace_bytes, g2s_stream_t stream);
+
 /* ----------------------------------------------------------------------------------------
  * ADA augmentation (csrc/ada.hip): random_apply_affine and random_apply_color of stylegan2-pytorch/non_leaking.py
  * with the SYM6 filter k (12 taps), f32, NCHW, two launches forward and two backward.
