@@ -56,6 +56,7 @@ SOURCES = {
     "resample.hip": [],
     "bank.hip": [],
     "mvn.hip": [],
+    "monitor.hip": ["-ffp-contract=off"],        # the grid's quantiser rounds step by step, as generate._quantise_torch
     "probe.hip": [],
 }
 # The kernels take their descriptor struct by value.  Clang copies such a parameter into a private

@@ -158,6 +158,8 @@ SIGNATURES = {
     "g2s_resample_sep": (_i, [_p, _p] + [_i] * 5 + [_p, _p, _p, _i, _p, _p, _p, _i, _p]),
     "g2s_bank_gather": (_i, [_p, _p, _i64, _p, _i, _i, _p, _i, _p, _p, _i, _p, _p]),
     "g2s_mvn_fit": (_i, [_p, _i64, _i, _i64, _p, _i, _d, _p, _p, _p, _p, _p]),
+    "g2s_image_grid_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _f, _f, _f, _p]),
+    "g2s_ppl_latents": (_i, [_p, _p, _f, _i, _p, _i, _i, _p]),
 }
 
 

@@ -3,12 +3,23 @@
 
     python -m gan2shape_amd.train --size 128 --channel-multiplier 1 --data root/car --iter 2000 --batch 16 \
         [--ckpt G_D.pt] [--augment] [--mixing 0.9] [--path-regularize 2] [--g-reg-every 4] [--save-every 10000] \
+        [--sample-every 100 [--n-sample 64] [--sample-dir DIR]] \
+        [--ppl-every 1000 --lpips-lin vgg.pth --lpips-vgg vgg16.pth [--ppl-samples 512]] \
         [--deterministic] --out ckpts/train.pt
 
 The checkpoint has train.py's keys: g, d, g_ema, g_optim, d_optim, ada_aug_p.  Without --ckpt the weights are fresh
-(torch.manual_seed(--seed)) and g_ema starts as a copy of g (train.py:419-421).  Not built: distributed training,
-wandb, sample grids, fp16."""
+(torch.manual_seed(--seed)) and g_ema starts as a copy of g (train.py:419-421).
+
+Monitoring (monitor.py), off by default: every --sample-every-th iteration g_ema's images of a fixed `sample_z` go to
+<sample dir>/%06d.png as one grid (train.py:303-316), every --ppl-every-th iteration the perceptual path length of
+g_ema (w space, full sampling) goes on the log line and into <dir of --out>/ppl.jsonl.  sample_z and the path
+length's draws come from generators of their own, seeded with --seed, and g_ema runs on its fixed noise buffers: the
+global random stream, and with it the trained weights, are the same with monitoring on or off.
+
+Not built: distributed training, wandb, fp16."""
 import argparse
+import contextlib
+import json
 import math
 import os
 
@@ -48,6 +59,15 @@ def build_parser():
     parser.add_argument("--log-every", dest="log_every", type=int, default=100)
     parser.add_argument("--save-every", dest="save_every", type=int, default=10000,
                         help="also write --out every this many iterations (train.py: 10000); 0: only at the end")
+    parser.add_argument("--sample-every", dest="sample_every", type=int, default=0,
+                        help="write a grid of g_ema samples every this many iterations (train.py: 100); 0: never")
+    parser.add_argument("--n-sample", dest="n_sample", type=int, default=64)
+    parser.add_argument("--sample-dir", dest="sample_dir", default=None, help="default: <dir of --out>/sample")
+    parser.add_argument("--ppl-every", dest="ppl_every", type=int, default=0,
+                        help="measure g_ema's perceptual path length every this many iterations; 0: never")
+    parser.add_argument("--ppl-samples", dest="ppl_samples", type=int, default=512)
+    parser.add_argument("--lpips-lin", dest="lpips_lin", default=None, help="lpips/weights/v0.1/vgg.pth")
+    parser.add_argument("--lpips-vgg", dest="lpips_vgg", default=None, help="a torchvision vgg16 state dict")
     parser.add_argument("--device", default="cuda")
     parser.add_argument("--out", required=True)
     return parser
@@ -99,8 +119,79 @@ def iteration(dt, gt, real_img, i):
     return loss
 
 
-def main(argv=None):
+@contextlib.contextmanager
+def _frozen(module):
+    """`module` as it is NOW, in eval mode with no parameter requiring a gradient (what the generator's one-node path
+    asks for); both are put back on exit.
+
+    A frozen forward keeps what it derives from the weights (the scaled weights of EqualLinear and ModulatedConv2d,
+    their squared sums, the style and mapping stacks) and knows them stale by `(data_ptr, _version)`.  The moving
+    average writes g_ema through `.data` (gtrain.accumulate), which moves neither, so every tensor's version is
+    advanced here: a host-side counter, no launch, and nothing the training path reads."""
+    torch.autograd.graph.increment_version(list(module.parameters()) + list(module.buffers()))
+    flags = [(p, p.requires_grad) for p in module.parameters()]
+    training = module.training
+    module.eval().requires_grad_(False)
+    try:
+        yield module
+    finally:
+        for p, flag in flags:
+            p.requires_grad_(flag)
+        module.train(training)
+
+
+class Monitor:
+    """The sample grids and path lengths of a run.  Draws nothing from the global generators."""
+
+    def __init__(self, args, g_ema, device, percept=None):
+        self.args, self.g_ema, self.device = args, g_ema, device
+        out_dir = os.path.dirname(os.path.abspath(args.out))
+        self.sample_dir = args.sample_dir or os.path.join(out_dir, "sample")
+        self.ppl_path = os.path.join(out_dir, "ppl.jsonl")
+        self.sample_z, self.percept = None, percept
+        if args.sample_every:
+            if args.n_sample < 1:
+                raise SystemExit("train: --n-sample must be positive")
+            g = torch.Generator(device=device).manual_seed(args.seed)
+            self.sample_z = torch.randn(args.n_sample, args.latent, device=device, generator=g)
+            os.makedirs(self.sample_dir, exist_ok=True)
+        if args.ppl_every and percept is None:
+            from .lpips import PerceptualLoss
+            self.percept = PerceptualLoss(lin_weights_path=args.lpips_lin, vgg_weights_path=args.lpips_vgg)
+        if self.percept is not None:
+            self.percept = self.percept.to(device).eval()
+
+    @staticmethod
+    def check_args(args, percept=None):
+        if args.ppl_every and percept is None and not (args.lpips_lin and args.lpips_vgg):
+            raise SystemExit("train: --ppl-every needs --lpips-lin and --lpips-vgg (a path length under random LPIPS "
+                             "weights is not a PPL)")
+
+    def samples(self):
+        with torch.no_grad(), _frozen(self.g_ema) as g:
+            return g([self.sample_z])[0]
+
+    def after(self, i):
+        """What iteration i leaves behind; returns the text to add to its log line."""
+        from . import monitor
+        args, text = self.args, ""
+        if args.sample_every and i % args.sample_every == 0:
+            monitor.save_grid(self.samples(), os.path.join(self.sample_dir, "%06d.png" % i),
+                              nrow=max(int(args.n_sample ** 0.5), 1))
+        if args.ppl_every and i % args.ppl_every == 0:
+            g = torch.Generator(device=self.device).manual_seed(args.seed)    # the same pairs at every measurement
+            with _frozen(self.g_ema) as g_ema:
+                r = monitor.perceptual_path_length(g_ema, self.percept, args.ppl_samples, generator=g)
+            with open(self.ppl_path, "a") as f:
+                f.write(json.dumps({"iter": i, **{k: r[k] for k in ("ppl", "n", "kept", "lo", "hi")}}) + "\n")
+            text = f" ppl {r['ppl']:.4f}"
+        return text
+
+
+def main(argv=None, percept=None):
+    """`percept`: a PerceptualLoss for --ppl-every to use instead of the one --lpips-lin / --lpips-vgg describe."""
     args = build_parser().parse_args(argv)
+    Monitor.check_args(args, percept)
     device = torch.device(args.device)
     torch.manual_seed(args.seed)
     if args.deterministic:
@@ -109,14 +200,16 @@ def main(argv=None):
     dt, gt = build_trainers(args, device)
     reals = dtrain.batches(args.data, args.size, args.batch, torch.Generator().manual_seed(args.seed), device)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    watch = Monitor(args, gt.g_ema, device, percept) if args.sample_every or args.ppl_every else None
     for i in range(args.iter):
         loss = iteration(dt, gt, next(reals).to(device), i)
+        seen = watch.after(i) if watch is not None else ""
         if args.save_every and i and i % args.save_every == 0:
             torch.save(checkpoint(dt, gt), args.out)
-        if args.log_every and (i % args.log_every == 0 or i == args.iter - 1):
+        if seen or (args.log_every and (i % args.log_every == 0 or i == args.iter - 1)):
             print(f"{i}: d {loss['d'].item():.4f} g {loss['g'].item():.4f} r1 {loss['r1'].item():.4f} "
                   f"path {loss['path'].item():.4f} mean path {float(gt.mean_path_length):.4f} "
-                  f"augment {dt.ada_aug_p:.4f}")
+                  f"augment {dt.ada_aug_p:.4f}{seen}")
             if not all(math.isfinite(float(v)) for v in loss.values()):
                 raise FloatingPointError(f"step {i}: a loss is not finite")
     torch.save(checkpoint(dt, gt), args.out)

@@ -1207,6 +1207,35 @@ int g2s_bank_gather(const float *bank_img, const float *bank_mask, long rows, co
 int g2s_mvn_fit(const float *rows, long N, int D, long ld, const int *blocks, int nblk, double ridge,
                 float *mean, float *cov, float *tril, int *status, g2s_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training monitor (csrc/monitor.hip; monitor.py: sample grids and the perceptual path length).
+ *
+ * g2s_image_grid_u8: x [N, C, H, W] f32, C in {1, 3}  ->  out [Hg, Wg, 3] uint8, the grid that torchvision's
+ *   save_image(x, nrow=, padding=, normalize=True, range=(lo, hi), pad_value=) writes, in ONE launch:
+ *     xmaps = min(nrow, N), ymaps = ceil(N / xmaps), Hg = ymaps (H + padding) + padding, Wg = xmaps (W + padding) + padding;
+ *     image k has its top-left pixel at ((k / xmaps) (H + padding) + padding, (k % xmaps) (W + padding) + padding);
+ *     a value v becomes  u = (clamp(v, lo, hi) - lo) / max(hi - lo, 1e-5);  uint8(clamp(u * 255 + 0.5, 0, 255)),
+ *     every step rounded to f32, truncated; C = 1 fills the three channels with the one value;
+ *     every other pixel, the cells after the last image included, is uint8(clamp(pad_value * 255 + 0.5, 0, 255)).
+ *   N == 1 gives the bare image: Hg = H, Wg = W, no border (make_grid returns early).
+ *   Every byte of out is written exactly once: no memset is needed.  No atomics, no workspace; capturable.
+ *   Hg * Wg < 2^31.  lo, hi, pad_value must not be NaN; a NaN in x gives an unspecified byte.
+ *
+ * g2s_ppl_latents: pairs [2B, D] f32 (rows 2i, 2i + 1 = the ends a, b of pair i), t [B] f32  ->  out [2B, D]:
+ *   row 2i is the point at t[i], row 2i + 1 the point at t1 = t[i] + eps, that sum rounded to f32.
+ *     mode 0 (w):  a + (b - a) * t
+ *     mode 1 (z):  n(x) = x / sqrt(sum x^2);  a = n(a), b = n(b), d = sum(a b), p = t acos(d), c = n(b - d a),
+ *                  n(a cos p + c sin p)
+ *   ONE launch, one 64-lane wave per pair, both rows from one read of the pair (D <= 512; longer rows are read again
+ *   by each pass).  The arithmetic is double, the sums fixed-order butterflies: no atomics, bit-identical from run to
+ *   run in every mode.  Any D >= 1; 16-byte accesses when D % 4 == 0 and pairs and out are 16-byte aligned.
+ *   out must not overlap pairs.  Parallel ends (a = +-b up to scale) give NaN in mode 1, as the formula does.
+ * ---------------------------------------------------------------------------------------- */
+int g2s_image_grid_u8(const float *x, uint8_t *out, int N, int C, int H, int W, int nrow, int padding,
+                      float lo, float hi, float pad_value, g2s_stream_t stream);
+int g2s_ppl_latents(const float *pairs, const float *t, float eps, int mode, float *out, int B, int D,
+                    g2s_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
